@@ -12,7 +12,16 @@
 
 value = bytes of input vectors reduced per second over the whole job
 (N x bytes per rank per step / step time), GiB/s.  Inputs are resident in HBM
-before the timed region.  Every run checks one untimed step against the
+before the timed region.
+
+A plain run does what the line's headline needs and no more: inputs, W warmup
+steps, K timed steps, the line.  --dump-outputs DIR also writes what the last
+timed step returned (dump_sample).  Everything else -- the parity check, the
+CPU baseline, the event-per-step pass, the combine-kernel rates and HBM
+ceilings at N = 1, the per-phase breakdown, the other configs and RCCL's own
+reduction at N > 1 -- runs with --full only, after the timed region.
+
+Every --full run checks one untimed step against the
 reference computed on the host by the cpu_baseline leg ("parity"): at N = 1
 the oracle's MPIR_SUM of the same inputs, at N > 1 the reference schedule
 on p host threads (one per rank), which is also the timed cpu_baseline.  The
@@ -73,13 +82,21 @@ def parse(argv=None):
     ap.add_argument("--launch-grace", type=float, default=30.0,
                     help="self-launched N > 1: seconds the other workers get after one fails before they "
                          "are killed")
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=50, help="timed steps (K)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default=None, choices=["c2", "c3", "c4", "c5"],
                     help="c2 at N = 1, c3 at N > 1 by default")
     ap.add_argument("--mib", type=int, default=0, help="vector MiB per rank (0 = the config's)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything the line's headline does not need, after the timed region: "
+                         "parity against the reference, the CPU baseline, the event-per-step pass "
+                         "(step_ms.evented_*), at N = 1 the combine-kernel rates and HBM ceilings, at "
+                         "N > 1 the per-phase breakdown, the other configs and RCCL's own reduction")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to DIR/<name>.npy "
+                         "(float32 / float64; a fixed seeded sample of a large result, dump_sample)")
     ap.add_argument("--no-cpu-baseline", action="store_true",
-                    help="skip the CPU leg (and with it the parity check against it)")
+                    help="--full: skip the CPU leg (and with it the parity check against it)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--prewarm-ms", type=float, default=0.0,
                     help="N = 1: untimed back-to-back steps for this long before the W warmup steps "
@@ -106,19 +123,22 @@ def parse(argv=None):
                     help="N > 1: seconds one checked step of an exchange variant may take before the "
                          "variant counts as hung (its communicator is aborted and rebuilt)")
     ap.add_argument("--no-native", action="store_true",
-                    help="N > 1: skip the RCCL-native reduction timed after the line (SURVEY.md 8(e) ablation)")
+                    help="N > 1, --full: skip the RCCL-native reduction timed after the line (SURVEY.md 8(e) "
+                         "ablation)")
     ap.add_argument("--host-e2e", action="store_true",
                     help="N = 1: also time the op on host buffers (PCIe-inclusive) after the timed region; "
                          "off by default: it launches the measured kernel template on PCIe-bound operands, "
                          "which would skew a kernel-trace average of the same command")
     ap.add_argument("--no-kernels", action="store_true",
-                    help="N = 1: skip the C3 / C4 / C5 combine-kernel rates after the timed region")
+                    help="N = 1, --full: skip the C3 / C4 / C5 combine-kernel rates after the timed region")
     ap.add_argument("--transport", default="rccl", choices=["rccl", "host", "rccl-net"],
                     help="host: ranks may share a GPU, bytes move through gloo; rccl-net: ranks may "
                          "share a GPU, bytes move through RCCL's own socket transport (each rank "
                          "names itself a separate host).  Both test the multi-GPU leg on a 1-GPU "
                          "box; neither is a performance configuration")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps needs at least 1 timed step, --warmup at least 0")
     if args.exchange != "auto":
         bad = [x for x in args.exchange.split(",") if x not in EXCH]
         if bad:
@@ -397,6 +417,58 @@ def synth(cfg, n, rank, device):
     return pair.view(-1).view(torch.uint8)
 
 
+# --------------------------------------------------------------- outputs ---
+
+DUMP_BYTES = 32 * MIB           # per run, over all ranks and arrays (the files stay under 64 MB)
+DUMP_EDGE = 4096                # the first and last elements are always in the sample
+
+
+def dump_sample(t, max_elems):
+    """A 1-D device tensor, or the (n, 2) view of one, as a host numpy array:
+    all of it up to max_elems elements (rows), else a fixed sample of that
+    many -- the first and last DUMP_EDGE and indices drawn with replacement
+    from a seeded host generator, the same for every run of the same size."""
+    import torch
+    n = t.shape[0]
+    if n <= max_elems:
+        return t.cpu().numpy()
+    g = torch.Generator()
+    g.manual_seed(0x5EED0000 + (n & 0xFFFF))
+    idx = torch.randint(0, n, (max_elems,), generator=g, dtype=torch.int64)
+    edge = min(DUMP_EDGE, max_elems // 2)
+    idx[:edge] = torch.arange(edge)
+    idx[max_elems - edge:] = torch.arange(n - edge, n)
+    return t[idx.to(t.device)].cpu().numpy()
+
+
+def dump_result(cfg, buf, world):
+    """{name: array} of one rank's result of config cfg (its bytes on the
+    device) at N > 1, in float32 / float64 only: c3 the float32 sums; c4 each
+    int64 word as its two 32-bit halves (low, high) in float64, which holds
+    them exactly; c5 the pairs' float32 values and their int32 locations in
+    float64."""
+    import numpy as np
+    import torch
+    share = DUMP_BYTES // world
+    if cfg == "c3":
+        return {"recv": dump_sample(buf.view(torch.float32), share // 4)}
+    if cfg == "c4":
+        w = dump_sample(buf.view(torch.int64), share // 16)
+        return {"recv_halves": w.view(np.int32).reshape(-1, 2).astype(np.float64)}
+    pair = dump_sample(buf.view(torch.int32).view(-1, 2), share // 12)
+    return {"recv_value": np.ascontiguousarray(pair[:, 0]).view(np.float32),
+            "recv_loc": pair[:, 1].astype(np.float64)}
+
+
+def write_dump(path, arrays, rank=None):
+    """DIR/<name>.npy at N = 1, DIR/<name>_rank<r>.npy for rank r at N > 1"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), a.dtype
+        np.save(os.path.join(path, name + ("" if rank is None else "_rank%d" % rank) + ".npy"), a)
+
+
 # ------------------------------------------------------------------- N = 1 --
 
 def cpu_baseline_op(n_bytes, seconds):
@@ -482,8 +554,10 @@ def run_single(args, mvx, dev, clock):
     x_in = [synth_f32(n, 0x9E3779B9 ^ (2 * s * 1000003 + 1), dev) for s in range(args.sets)]
     x_io = [synth_f32(n, 0x9E3779B9 ^ ((2 * s + 1) * 1000003 + 1), dev) for s in range(args.sets)]
     # the parity check reads set 0 before any step has touched it
-    keep = None if args.no_cpu_baseline else (x_in[0].clone(), x_io[0].clone())
+    check = args.full and not args.no_cpu_baseline
+    keep = (x_in[0].clone(), x_io[0].clone()) if check else None
     it = [0]
+    dump = {}
 
     def step():
         s = it[0] % args.sets
@@ -496,9 +570,18 @@ def run_single(args, mvx, dev, clock):
     # host-side parity check and the CPU leg run after the timed region
     torch.cuda.synchronize()
     clock.mark("inputs")
+    def last_output():
+        # what the caller of the last timed step holds: that step's inout
+        # vector (before --full's evented pass adds to it again)
+        if args.dump_outputs:
+            dump["inout"] = dump_sample(x_io[(it[0] - 1) % args.sets], DUMP_BYTES // 4)
+
     warm = prewarm(args, step)
-    times = timed(args, step, stream, 1)
+    times = timed(args, step, stream, 1, evented=args.full, after_timed=last_output)
     clock.mark("timed steps")
+    if args.dump_outputs:
+        write_dump(args.dump_outputs, dump)
+        clock.mark("outputs written")
     # cpu_baseline leg, part 1: the reference op on the same inputs (checker)
     parity = None
     if keep is not None:
@@ -513,9 +596,9 @@ def run_single(args, mvx, dev, clock):
     roof = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
             "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": tsrc,
             "kernel": kernel, "kernel_symbol": symbol, "kernel_us": round(kern_s * 1e6, 2),
-            # per-launch distribution from the event-per-step pass (timed())
-            "kernel_us_evented_median": round(times["median_ms"] * 1e3, 2),
-            "kernel_us_evented_min": round(times["min_ms"] * 1e3, 2),
+            # per-launch distribution from the event-per-step pass (timed(), --full)
+            "kernel_us_evented_median": _round(times["median_ms"], 2, 1e3),
+            "kernel_us_evented_min": _round(times["min_ms"], 2, 1e3),
             "alg_bytes_per_launch": alg_bytes}
     out = result(args, 1, nbytes, times, "f32",
                  {"workload": "config2: device-resident pairwise MPI_SUM float32 %d MiB (local MPI_Op kernel), "
@@ -524,14 +607,18 @@ def run_single(args, mvx, dev, clock):
                   "parallelism": "single GPU"}, roof)
     out["parity"] = parity
     out["prewarm"] = warm
-    if not args.no_cpu_baseline:
+    out["full"] = args.full
+    if check:
         out["cpu_baseline"] = cpu_baseline_op(nbytes, args.cpu_seconds)
-    if not args.no_kernels:
+    if args.full and not args.no_kernels:
         out["combine_kernels"] = combine_kernels(mvx)
         roof["mix_ceiling"] = mix_ceiling(x_in, x_io, nbytes, achieved, stream)
     if args.host_e2e:
         out["host_end_to_end"] = host_end_to_end(mvx, nbytes)
-    clock.mark("parity, cpu baseline, combine kernels, ceilings")
+    if args.full:
+        clock.mark("parity, cpu baseline, combine kernels, ceilings")
+    elif args.host_e2e:
+        clock.mark("host end to end")
     out["env"] = env_echo()
     out["wall"] = clock.report()
     print(json.dumps(out), flush=True)
@@ -653,12 +740,17 @@ class StepFailure(Exception):
                 "a step did not complete within %.0f s" % self.limit)
 
 
-def timed(args, step, stream, world, agree=None, limit=None):
+def _round(v, digits, scale=1.0):
+    return None if v is None else round(v * scale, digits)
+
+
+def timed(args, step, stream, world, agree=None, limit=None, evented=True, after_timed=None):
     """W untimed steps, then K steps between barrier + synchronize, with one
     HIP event pair on the launch stream around them (the mean: nothing else
-    is enqueued between the steps).  Then, untimed, K more steps with an
-    event after each for the median / min (an event between two kernels adds
-    a few microseconds of its own, so these are not used for the mean).
+    is enqueued between the steps).  after_timed() runs once they are done.
+    Then, if `evented` (--full), untimed, K more steps with an event after
+    each for the median / min (an event between two kernels adds a few
+    microseconds of its own, so these are not used for the mean).
 
     N > 1 (agree given): every block of steps ends in a bounded wait for the
     launch stream (busy polling, `limit` seconds) and a status agreement over
@@ -726,17 +818,21 @@ def timed(args, step, stream, world, agree=None, limit=None):
             raise StepFailure(worst, limit)
     wall = wall[0]
     dev_ms = e0.elapsed_time(e1)
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-    evs[0].record(stream)
-    settle(run(args.steps, evs))
-    per = [evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps)]
+    if after_timed is not None:
+        after_timed()
+    per = None
+    if evented:
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+        evs[0].record(stream)
+        settle(run(args.steps, evs))
+        per = [evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps)]
     t_local = max(wall, dev_ms / 1e3)
     if world > 1:
         t = torch.tensor([t_local], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         t_local = float(t.item())
     return {"t_job": t_local, "dev_ms": dev_ms, "mean_ms": dev_ms / args.steps,
-            "median_ms": statistics.median(per), "min_ms": min(per)}
+            "median_ms": statistics.median(per) if per else None, "min_ms": min(per) if per else None}
 
 
 def result(args, world, nbytes, times, dtype, config, roof):
@@ -746,9 +842,9 @@ def result(args, world, nbytes, times, dtype, config, roof):
         "value": round(world * nbytes * args.steps / times["t_job"] / GIB, 2), "unit": "GiB/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 5),
         "step_ms": {"mean": round(times["mean_ms"], 5),
-                    # a second, untimed pass of K steps with an event after each
-                    # (each event adds a few microseconds between steps)
-                    "evented_median": round(times["median_ms"], 5), "evented_min": round(times["min_ms"], 5)},
+                    # --full: a second, untimed pass of K steps with an event after
+                    # each (each event adds a few microseconds between steps)
+                    "evented_median": _round(times["median_ms"], 5), "evented_min": _round(times["min_ms"], 5)},
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype,
         "data": "synthetic (generated on device, SURVEY.md 8(d) distributions)",
         "config": config, "roofline": roof,
@@ -1096,7 +1192,7 @@ def run_multi(args, mvx, dev, world, rank, local, clock):
     torch.cuda.synchronize()
     clock.mark("inputs")
     it = [0]
-    cur = {"name": None, "comm": comm, "best": None}
+    cur = {"name": None, "comm": comm, "best": None, "dump": None}
 
     def step():
         s = it[0] % sets
@@ -1117,7 +1213,7 @@ def run_multi(args, mvx, dev, world, rank, local, clock):
     # cpu_baseline leg: the reference schedule on p host threads -- timed, and
     # its per-rank results are the parity reference
     ref, cpu = None, None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         if rank == 0:
             ref, secs, reps = reference_run(cfg, world, n, dev, True)
             cpu = {"value": round(world * nbytes / secs / GIB, 3), "unit": "GiB/s", "cores": world,
@@ -1181,16 +1277,26 @@ def run_multi(args, mvx, dev, world, rank, local, clock):
         cur["name"] = name
         apply_variant(cur["comm"], name)
         limit = step_limit(args, est_s)
-        times = timed(args, step, stream, world, agree, limit)
+        got = {}
+
+        def last_output():
+            # which receive buffer the last timed step filled: copied to the
+            # host only if this variant becomes the line (take_dump).  The
+            # untimed steps --full runs after it repeat the same call on the
+            # same inputs, so the buffer holds the same bytes then.
+            got["set"] = (it[0] - 1) % sets
+
+        times = timed(args, step, stream, world, agree, limit, evented=args.full, after_timed=last_output)
         ran = EXCH_NAMES.get(cur["comm"].last_exchange(), "?")
         graph = GRAPH_STATES.get(cur["comm"].last_graph()[0]) if EXCH[name][2] else None
         # set 0's result as the timed steps left it (graph replays included)
         # against the reference again
         post = parity_check()
         pb = plan_bytes(mvx, coll, world, rank, n, cnts, dtype, op)
-        status = 0
+        status, phases = 0, None
         try:
-            phases = phase_breakdown(cur["comm"], step, coll, world, nbytes, pb, stream, agree, limit)
+            if args.full:
+                phases = phase_breakdown(cur["comm"], step, coll, world, nbytes, pb, stream, agree, limit)
         except StepFailure as e:
             phases, status = {"error": "phase-timing steps: " + e.text()}, e.worst
         p = world
@@ -1220,7 +1326,8 @@ def run_multi(args, mvx, dev, world, rank, local, clock):
                          else ("MISMATCH" if parity is False else None))
         out["parity_after_timed"] = post
         out["cpu_baseline"] = cpu
-        return out, status
+        out["full"] = args.full
+        return out, status, got
 
     # Exchange variants in EXCH order (p2p first, coll last).  Each gets one
     # checked step, then --tune-steps timed steps if every rank completed it
@@ -1327,7 +1434,7 @@ def run_multi(args, mvx, dev, world, rank, local, clock):
             box = [name]
             dist.broadcast_object_list(box, src=0)
             try:
-                cand, pstat = measure(box[0], max(est, entry["ms_per_step"] * 1e-3))
+                cand, pstat, got = measure(box[0], max(est, entry["ms_per_step"] * 1e-3))
             except StepFailure as e:
                 entry.update(ms_per_step=None, error="timed steps: " + e.text())
                 recover(e.worst, entry)
@@ -1337,6 +1444,8 @@ def run_multi(args, mvx, dev, world, rank, local, clock):
                 entry.update(parity=False, error="MISMATCH in the result the timed steps left")
             elif best is None or cand["ms_per_step"] < best["ms_per_step"]:
                 cur["best"] = cand
+                if args.dump_outputs:
+                    cur["dump"] = dump_result(cfg, recvbuf[got["set"]], world)
             if pstat:
                 entry["error"] = cand["roofline"]["phases"]["error"]
                 recover(pstat, entry)
@@ -1346,10 +1455,15 @@ def run_multi(args, mvx, dev, world, rank, local, clock):
         if rank == 0:
             sys.stderr.write("bench: no exchange variant ran clean with parity: %s\n" % json.dumps(tried))
         return None, emit
-    # the other BASELINE configs quoted at this GPU count, on the same
+    if args.dump_outputs:
+        write_dump(args.dump_outputs, cur["dump"], rank)
+        clock.mark("outputs written")
+    # --full: the other BASELINE configs quoted at this GPU count, on the same
     # communicator and exchange variant, after the line's timed region
     extras = EXTRA_AT.get(world, []) if args.extra_configs == "auto" else \
         [c for c in args.extra_configs.split(",") if c and c != "none"]
+    if not args.full:
+        extras = []
     others, aborted = [], False
     for cfg2 in extras:
         if cfg2 == cfg:
@@ -1364,7 +1478,7 @@ def run_multi(args, mvx, dev, world, rank, local, clock):
             break
     if others:
         out["other_configs"] = others
-    if not aborted and not args.no_native and args.transport != "host":
+    if args.full and not aborted and not args.no_native and args.transport != "host":
         nat, worst = rccl_native(args, mvx, cur["comm"], cfg, n, sendbuf[0], world, dev, stream, agree,
                                  out["ms_per_step"])
         if nat is not None:

@@ -205,6 +205,42 @@ def test_mix_ceiling_summary():
     assert copy < d["mixed_line_GBs"] < read
 
 
+def test_dump_sample_is_fixed_and_keeps_the_edges(tmp_path):
+    """bench.dump_sample: a small result whole; a large one as the same
+    indices every time, the first and last elements among them.
+    bench.write_dump: float32 / float64 .npy files, per rank at N > 1."""
+    import numpy as np
+    import torch
+    small = torch.arange(1000, dtype=torch.float32)
+    assert np.array_equal(bench.dump_sample(small, 1000), small.numpy())
+    n, k = 3 * bench.DUMP_EDGE * 4 + 7, 3 * bench.DUMP_EDGE
+    big = torch.arange(n, dtype=torch.float32)
+    a, b = bench.dump_sample(big, k), bench.dump_sample(big.clone(), k)
+    assert a.shape == (k,) and a.dtype == np.float32 and np.array_equal(a, b)
+    e = bench.DUMP_EDGE
+    assert np.array_equal(a[:e], np.arange(e)) and np.array_equal(a[-e:], np.arange(n - e, n))
+    assert len(np.unique(a[e:-e])) > e // 2 and a.max() < n        # a spread of indices in range
+    pairs = torch.arange(2 * n, dtype=torch.int32).view(-1, 2)
+    assert bench.dump_sample(pairs, k).shape == (k, 2)
+    # every config's result, in float32 / float64 only, within the byte budget
+    for cfg, esz in (("c3", 4), ("c4", 8), ("c5", 8)):
+        buf = torch.arange(4096 * esz, dtype=torch.int64).to(torch.uint8)
+        arrs = bench.dump_result(cfg, buf, 2)
+        assert all(v.dtype in (np.float32, np.float64) and len(v) == 4096 for v in arrs.values()), cfg
+        bench.write_dump(str(tmp_path), arrs, rank=1)
+    assert sorted(os.listdir(tmp_path)) == ["recv_halves_rank1.npy", "recv_loc_rank1.npy", "recv_rank1.npy",
+                                            "recv_value_rank1.npy"]
+    w = np.load(tmp_path / "recv_halves_rank1.npy")
+    assert w.shape == (4096, 2) and w.dtype == np.float64
+
+
+def test_full_and_dump_options_parse():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "0"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 0
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+
+
 _CHATTER = r'''
 import datetime, os, sys
 sys.path.insert(0, sys.argv[1])

@@ -214,7 +214,7 @@ def _bench_host(cfg, extra_env=None, world=2, transport="host", extra_args=()):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", str(world), "--steps", "3", "--warmup", "1", "--tune-steps", "1", "--mib", "32",
-           "--config", cfg, "--transport", transport] + list(extra_args)
+           "--config", cfg, "--transport", transport, "--full"] + list(extra_args)
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     return p
 
@@ -295,7 +295,7 @@ def test_bench_full_size_eight_ranks_rccl_net():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "8", "--steps", "2", "--warmup", "1", "--tune-steps", "1", "--transport", "rccl-net",
-           "--graphs"]
+           "--graphs", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=420)
     assert p.returncode == 0, p.stderr[-3000:]
     line = [x for x in p.stdout.splitlines() if x.startswith("{")]
@@ -371,7 +371,7 @@ def test_bench_line_carries_the_other_baseline_configs():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "4", "--steps", "2", "--warmup", "1", "--tune-steps", "1", "--mib", "16",
-           "--transport", "host"]
+           "--transport", "host", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=400)
     assert p.returncode == 0, p.stderr[-3000:]
     line = [x for x in p.stdout.splitlines() if x.startswith("{")]
@@ -391,7 +391,7 @@ def _bench_self(world, transport, extra=(), extra_env=None):
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     env.update(extra_env or {})
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
-           "--tune-steps", "1", "--mib", "16", "--transport", transport] + list(extra)
+           "--tune-steps", "1", "--mib", "16", "--transport", transport, "--full"] + list(extra)
     return subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=400)
 
 

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""Per-dispatch durations of one kernel across a bench.py N = 1 run, from a
+"""Per-dispatch durations of one kernel across a bench.py --full N = 1 run, from a
 rocprofv3 --kernel-trace CSV: which launches were the prewarm, the W warmup
 steps, the K timed steps, the K evented steps and the parity step, and what
 each segment averaged.
 
   tools/dispatch_series.py TRACE_DIR KERNEL_SUBSTRING K [OUT.json]
 
-bench.py's order at N = 1 is: prewarm (any count), W warmup, K timed, K
+bench.py --full's order at N = 1 is: prewarm (any count), W warmup, K timed, K
 evented, 1 parity step -- so the segments are read from the END of the
 series, and the count of the prewarm/warmup part is whatever precedes them.
 """

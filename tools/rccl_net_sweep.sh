@@ -7,7 +7,7 @@
 #   MVX_MP_CASES=300 WORLDS="3 5 6 8" tools/rccl_net_sweep.sh
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out
+mkdir -p ${OUT:-${MVX_OUT:-out}}     # the caller redirects the lines there (tools/gpu_round.sh)
 export MVX_MP_CASES=${MVX_MP_CASES:-300}
 export WORLDS=${WORLDS:-3 5 6 8}
 timeout -k 10 1000 python -u - <<'PY'
