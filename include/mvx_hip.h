@@ -172,6 +172,11 @@ const char *mvx_hip_last_kernel_symbol(void);
 /* grid blocks, dynamic LDS bytes (the residency cap) and resident blocks per
  * CU (the runtime's occupancy answer) of the last launch */
 void mvx_hip_last_launch(unsigned *blocks, size_t *dynamic_lds, int *blocks_per_cu);
+/* The same for the datatype engine: the template mvx_type_pack /
+ * mvx_type_unpack last launched ("k_pack_tiles<4, 8192, true, false,
+ * false>", "k_unpack_merge<...>", "k_pack_units<...>", "k_pack<true>"), or
+ * "memcpy" for a basic type; "" before the first call. */
+const char *mvx_type_last_kernel_symbol(void);
 
 #ifdef __cplusplus
 }

@@ -210,6 +210,7 @@ def _load():
     _hip.mvx_type_layout.argtypes = [i, pi, pi, pl, pl, pl, pl]
     _hip.mvx_type_pack.argtypes = [i, vp, vp, sz, vp]
     _hip.mvx_type_unpack.argtypes = [i, vp, vp, sz, vp]
+    _hip.mvx_type_last_kernel_symbol.restype = ctypes.c_char_p
     _hip.mvx_op_element_size.argtypes = [i, i]
     c.MPI_Type_commit.argtypes = [pi]
     c.mvx_type_set_handle.argtypes = [i, i]

@@ -18,6 +18,7 @@ __all__ = [
     "MPI_Type_contiguous", "MPI_Type_commit", "MPI_Type_free", "MPI_Type_extent", "MPI_Type_size",
     "MPI_Type_vector", "MPI_Type_hvector", "MPI_Type_indexed", "MPI_Type_hindexed", "MPI_Type_struct",
     "MPI_Type_lb", "MPI_Type_ub", "type_layout", "type_set_handle", "type_pack", "type_unpack",
+    "type_last_kernel_symbol",
 ]
 
 
@@ -452,6 +453,12 @@ def type_pack(datatype, origin, packed, count, stream=None):
 
 def type_unpack(datatype, packed, origin, count, stream=None):
     return hip().mvx_type_unpack(datatype, addr(packed), addr(origin), count, stream_handle(stream))
+
+
+def type_last_kernel_symbol():
+    """The pack / unpack kernel template last launched, as rocprofv3 names it
+    ("memcpy" for a basic type)."""
+    return hip().mvx_type_last_kernel_symbol().decode()
 
 
 def MPI_Type_commit(datatype):

@@ -26,6 +26,7 @@
 // (initdte.c:106-280, MPIR_Setup_base_datatype 281-310).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
@@ -527,6 +528,28 @@ bool info(int h, Info *out)
 
 struct DBlk { long off, poff; int len, pad; };
 
+// The last pack / unpack kernel launched, as rocprofv3 names the template
+// (mvx_type_last_kernel_symbol; "memcpy" for a basic type): each spelling is
+// formatted once and kept, so a launch only stores a pointer.
+static const char *g_last_sym = "";
+static const char *tf(bool b) { return b ? "true" : "false"; }
+// b0..b2: the kernel's three bool template arguments in template order
+static const char *sym_tile(const char *kernel, int W, int tile, bool b0, bool b1, bool b2)
+{
+    static char buf[2][5][8][64];
+    const int ki = kernel[2] == 'u', wi = W == 16 ? 0 : W == 8 ? 1 : W == 4 ? 2 : W == 2 ? 3 : 4;
+    char *s = buf[ki][wi][b0 * 4 + b1 * 2 + b2];
+    if (!s[0]) snprintf(s, 64, "%s<%d, %d, %s, %s, %s>", kernel, W, tile, tf(b0), tf(b1), tf(b2));
+    return s;
+}
+static const char *sym_units(bool pack, int W, int U, bool lds)
+{
+    static char buf[2][3][2][64];
+    char *s = buf[pack][W == 16 ? 0 : W == 8 ? 1 : 2][lds];
+    if (!s[0]) snprintf(s, 64, "k_pack_units<%s, %d, %d, %s>", tf(pack), W, U, tf(lds));
+    return s;
+}
+
 template <bool PACK>
 __global__ void __launch_bounds__(256)
 k_pack(const char *__restrict__ src, char *__restrict__ dst, const DBlk *__restrict__ map, long nblk,
@@ -711,6 +734,7 @@ static int launch_units(const Type &t, int wi, const void *src, void *dst, long 
     if (blocks > 65536) blocks = 65536;
     if (blocks < 1) blocks = 1;
     const long T = blocks * 256;
+    g_last_sym = sym_units(PACK, W, U, upe <= UNITS_LDS);
     if (upe <= UNITS_LDS)
         hipLaunchKernelGGL((k_pack_units<PACK, W, U, true>), dim3((unsigned)blocks), dim3(256), 0, st,
                            (const char *)src, (char *)dst, (const int *)t.dunits[wi], upe, count, t.extent, T / upe,
@@ -978,9 +1002,12 @@ static int launch_merge(Type &t, int wi, const void *src, void *dst, long count,
     if (tiles < 1 || tiles > INT32_MAX) return MPI_ERR_OTHER;
     const int sw = swz_on() ? t.swz[wi] : 0;
 #define MVX_MERGE_LAUNCH(LU, SW, TB)                                                                               \
-    hipLaunchKernelGGL((k_unpack_merge<W, MERGE_TILE, LU, SW, TB>), dim3((unsigned)tiles), dim3(256), 0, st,       \
-                       (const char *)src, (char *)dst, (const int *)t.dunits[wi], upe, count, t.extent, lo, hi, a0, \
-                       h0, h1, sw, t.tabP[wi])
+    do {                                                                                                           \
+        g_last_sym = sym_tile("k_unpack_merge", W, MERGE_TILE, LU, SW, TB);                                        \
+        hipLaunchKernelGGL((k_unpack_merge<W, MERGE_TILE, LU, SW, TB>), dim3((unsigned)tiles), dim3(256), 0, st,   \
+                           (const char *)src, (char *)dst, (const int *)t.dunits[wi], upe, count, t.extent, lo, hi, \
+                           a0, h0, h1, sw, t.tabP[wi]);                                                            \
+    } while (0)
     // the chunk table for 1- and 2-byte units (as k_pack_tiles; MVX_PACK_CHUNK_TAB)
     const bool tb = merge_tab_on() && W <= 2 && t.tabP[wi] > 0;
     if (tb) {
@@ -1129,9 +1156,12 @@ static int launch_tiles(Type &t, int wi, const void *src, void *dst, long count,
     const long tiles = (count + ept - 1) / ept;
     if (tiles < 1 || tiles > INT32_MAX) return MPI_ERR_OTHER;
 #define MVX_PACK_TILES_LAUNCH(LU, TB, SW)                                                                        \
-    hipLaunchKernelGGL((k_pack_tiles<W, PACK_TILE, LU, TB, SW>), dim3((unsigned)tiles), dim3(256), 0, st,          \
-                       (const char *)src, (char *)dst, (const int *)t.dunits[wi], t.units[wi], count, t.extent, lo,  \
-                       hi, ept, t.tabP[wi], sw)
+    do {                                                                                                         \
+        g_last_sym = sym_tile("k_pack_tiles", W, PACK_TILE, LU, TB, SW);                                         \
+        hipLaunchKernelGGL((k_pack_tiles<W, PACK_TILE, LU, TB, SW>), dim3((unsigned)tiles), dim3(256), 0, st,      \
+                           (const char *)src, (char *)dst, (const int *)t.dunits[wi], t.units[wi], count, t.extent, \
+                           lo, hi, ept, t.tabP[wi], sw);                                                         \
+    } while (0)
     // MVX_PACK_CHUNK_TAB=0: the unit offsets stepped per unit (A/B)
     static int tab_on = -1;
     if (tab_on < 0) {
@@ -1187,6 +1217,7 @@ static int pack(int h, const void *src, void *dst, size_t count, hipStream_t st,
         // a basic type is its own packed form
         if (!basic(h, v)) return MPI_ERR_TYPE;
         if (!count || !v.size) return MPI_SUCCESS;
+        g_last_sym = "memcpy";
         if (v.map.size() == 1)
             return hipMemcpyAsync(dst, src, count * (size_t)v.size, hipMemcpyDeviceToDevice, st) == hipSuccess
                    ? MPI_SUCCESS : MPI_ERR_OTHER;
@@ -1261,6 +1292,7 @@ static int pack(int h, const void *src, void *dst, size_t count, hipStream_t st,
     const long items = (long)count * t->dmap_n;
     long blocks = (items + 255) / 256;
     if (blocks > 65536) blocks = 65536;
+    g_last_sym = packing ? "k_pack<true>" : "k_pack<false>";
     if (packing)
         hipLaunchKernelGGL(k_pack<true>, dim3((unsigned)blocks), dim3(256), 0, st, (const char *)src, (char *)dst,
                            (const DBlk *)t->dmap, t->dmap_n, (long)count, t->extent, t->size);
@@ -1370,3 +1402,5 @@ extern "C" int mvx_type_unpack(int type, const void *packed, void *origin, size_
 {
     return pack(type, packed, origin, count, (hipStream_t)stream, false);
 }
+
+extern "C" const char *mvx_type_last_kernel_symbol(void) { return g_last_sym; }

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import mvxtest as T
+import small_launch as SL
 from plan_exec import SHAPE_CHAIN, SHAPE_TREE, combine_cpu
 
 pytestmark = pytest.mark.gpu
@@ -18,16 +19,7 @@ NT_ELEMS = 4 << 20          # 16 MiB of f32 per leaf: a non-temporal launch at k
 def _run(mvx, op, dtype, k, shape, n, offset=0, folded=False, seed=0, ties=0.0):
     import torch
     E = mvx.dtype_info(dtype)[0]
-    S = [T.rand_vec(dtype, n, 100 * seed + q) for q in range(k)]
-    if ties:
-        # equal values across leaves (x87 fields: the loc = min rule), a
-        # fraction `ties` of the elements of each leaf copied from the last
-        rng = np.random.default_rng(seed + 77)
-        for q in range(1, k):
-            sel = rng.random(n) < ties
-            cur, prev = S[q].view(np.uint8).reshape(n, -1), S[q - 1].view(np.uint8).reshape(n, -1)
-            cur[sel, :10] = prev[sel, :10]          # significand + sign / exponent
-    F = [T.rand_vec(dtype, n, 100 * seed + 50 + q) if folded and q % 2 else None for q in range(k)]
+    S, F = SL.leaves(dtype, k, n, seed, ties, folded)      # ties: equal x87 values, the loc = min rule
     # device leaves at byte `offset` into their allocation (offset 4 breaks the
     # 16-byte body for 4-byte types: head elements, k_combine)
     def dev(x):
@@ -67,7 +59,9 @@ def test_body_dispatch_and_bits(mvx, op, dtype, k, shape):
         assert np.array_equal(got, ref)
 
 
-def test_body_not_used_for_folds_small_or_disabled(mvx, monkeypatch):
+def test_body_not_used_for_folds_small_or_disabled(mvx):
+    """Folded leaves and cached (small) launches run k_combine.  The disabled
+    case (MVX_NO_BODY=1, read once per process) lives in test_gpu_knobs.py."""
     n = NT_ELEMS
     sym, got, ref = _run(mvx, 102, 10, 8, SHAPE_TREE, n, folded=True)
     assert sym.startswith("k_combine<") and np.array_equal(got, ref)
@@ -145,13 +139,19 @@ def test_one_byte_types_swar(mvx, op, dtype, k, shape):
     wrapping SUM / PROD, signed and unsigned MAX / MIN, the logical ops'
     0 / 1 bytes, the bitwise ops) in every kernel family -- the plain op,
     the masked program, the tree and chain bodies -- bit for bit against the
-    oracle, at a non-temporal size and at a small one with head / tail
-    elements around the 16-byte body."""
+    oracle, at a non-temporal size that is a whole number of chunks (the
+    body kernels at k = 4 and 8, by symbol), at a ragged one (k_combine) and
+    at a small one with head / tail elements around the 16-byte body."""
     E = mvx.dtype_info(dtype)[0]
     assert E == 1
-    for n, off in ((NT_ELEMS * 4 + 3, 0), (4099, 5)):
+    for n, off in ((NT_ELEMS * 4, 0), (NT_ELEMS * 4 + 3, 0), (4099, 5)):
         sym, got, ref = _run(mvx, op, dtype, k, shape, n, offset=off, seed=k)
         assert np.array_equal(got, ref), (sym, n)
+        if n == NT_ELEMS * 4 and k in (4, 8):
+            pre, suf = SL.body_symbol(op, k, shape)
+            assert sym.startswith(pre) and sym.endswith(suf), sym
+        else:
+            assert sym.startswith("k_combine<"), sym
 
 
 @pytest.mark.parametrize("shape", [SHAPE_TREE, SHAPE_CHAIN])

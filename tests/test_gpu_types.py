@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import mvxtest as T
+import typemap_util as TM
 import uops
 
 pytestmark = pytest.mark.gpu
@@ -24,12 +25,7 @@ pytestmark = pytest.mark.gpu
 I, D, F, C, B = 6, 11, 10, 1, 3
 
 
-def _both(mvx, oracle, ctor, *args):
-    rm, hm = getattr(mvx, "MPI_Type_" + ctor)(*args)
-    ro, ho = getattr(oracle, "type_" + ctor)(*args)
-    assert rm == ro == 0 and hm == ho, (ctor, args, rm, ro)
-    assert mvx.MPI_Type_commit(hm) == 0 and oracle.type_commit(ho) == 0
-    return hm
+_both = TM.both
 
 
 def _types(mvx, oracle):
@@ -326,17 +322,7 @@ def test_whole_word_unpack_keeps_every_other_byte(mvx, oracle):
     for maps of 1- and 2-byte pieces (the tile kernels over 1- and 2-byte
     units)."""
     import torch
-    made = [
-        _both(mvx, oracle, "vector", 8, 1, 4, D),              # 8 B of every 32
-        _both(mvx, oracle, "vector", 2, 1, 2, F),              # every other float
-        _both(mvx, oracle, "struct", 2, [1, 1], [0, 8], [I, D]),  # {int; hole; double}
-        _both(mvx, oracle, "hvector", 3, 1, -20, I),           # reaches below the origin
-        _both(mvx, oracle, "hindexed", 3, [1, 2, 1], [0, 12, 40], F),
-        _both(mvx, oracle, "vector", 2, 1, 2, C),              # every other byte (1-byte units)
-        _both(mvx, oracle, "struct", 2, [1, 1], [0, 4], [C, I]),  # {char; hole; int}
-        _both(mvx, oracle, "hvector", 3, 1, 6, 4),             # shorts 6 bytes apart (2-byte units)
-        _both(mvx, oracle, "hindexed", 3, [3, 1, 2], [1, 9, 13], C),   # bytes from 1, odd spans
-    ]
+    made = TM.whole_word_types(mvx, oracle)
     try:
         for h in made:
             ext = mvx.MPI_Type_extent(h)[1]
@@ -373,47 +359,7 @@ def test_whole_word_unpack_keeps_every_other_byte(mvx, oracle):
             oracle.type_free(h)
 
 
-def _random_type(mvx, oracle, rng):
-    """A random hindexed / struct type of 1-, 2-, 4- and 8-byte pieces:
-    blocks in random order (the type map's order is the packed order),
-    gaps, sometimes reaching below the origin, sometimes nested in an
-    hvector whose stride leaves a gap.  Returns the handles to free."""
-    base = [(C, 1), (B, 1), (4, 2), (I, 4), (F, 4), (D, 8)]
-    nb = int(rng.integers(1, 6))
-    kind = "struct" if rng.random() < 0.4 else "hindexed"
-    if kind == "hindexed":
-        bt, bs = base[int(rng.integers(len(base)))]
-        types = [bt] * nb
-        sizes = [bs] * nb
-    else:
-        pick = [base[int(i)] for i in rng.integers(len(base), size=nb)]
-        types = [p[0] for p in pick]
-        sizes = [p[1] for p in pick]
-    lens = [int(x) for x in rng.integers(1, 5, size=nb)]
-    displs, cur = [], 0
-    for s, ln in zip(sizes, lens):
-        cur += int(rng.integers(0, 4)) * s          # a gap of whole pieces
-        cur = (cur + s - 1) // s * s
-        displs.append(cur)
-        cur += s * ln
-    if rng.random() < 0.25:                         # reach below the origin
-        shift = 8 * int(rng.integers(1, 4))
-        displs = [d - shift for d in displs]
-    order = rng.permutation(nb)
-    displs = [displs[i] for i in order]
-    lens = [lens[i] for i in order]
-    types = [types[i] for i in order]
-    if kind == "hindexed":
-        h = _both(mvx, oracle, "hindexed", nb, lens, displs, types[0])
-    else:
-        h = _both(mvx, oracle, "struct", nb, lens, displs, types)
-    made = [h]
-    if rng.random() < 0.3:
-        ext = mvx.MPI_Type_extent(h)[1]
-        stride = ext + 8 * int(rng.integers(0, 3))
-        h = _both(mvx, oracle, "hvector", int(rng.integers(2, 4)), 1, stride, h)
-        made.append(h)
-    return h, made
+_random_type = TM.random_type
 
 
 @pytest.mark.parametrize("batch", range(int(os.environ.get("MVX_FUZZ_TYPEMAP_BATCHES", "8"))))
@@ -470,10 +416,7 @@ def test_whole_word_unpack_of_large_elements(mvx, oracle):
     oracle's type-map copy with guard bands, at several counts and origin
     phases."""
     import torch
-    made = [
-        _both(mvx, oracle, "hindexed", 1100, [2] * 1100, [3 * i for i in range(1100)], C),
-        _both(mvx, oracle, "hindexed", 1400, [2] * 1400, [3 * i for i in range(1400)], C),
-    ]
+    made = TM.large_types(mvx, oracle)
     try:
         for h in made:
             ext = mvx.MPI_Type_extent(h)[1]
@@ -500,3 +443,73 @@ def test_whole_word_unpack_of_large_elements(mvx, oracle):
         for h in made:
             mvx.MPI_Type_free(h)
             oracle.type_free(h)
+
+
+# launch_merge's rows (LDSU, SWZ, TAB) and launch_tiles' rows (LDSU, TAB, SWZ),
+# mvx_dtype.hip; every one is reached below
+MERGE_ROWS = {(False, True, True), (False, False, True), (False, True, False), (False, False, False),
+              (True, True, False), (True, False, False)}
+TILES_ROWS = {(False, True, True), (False, True, False), (True, False, True), (True, False, False),
+              (False, False, True), (False, False, False)}
+# launch_tiles rows that no type map without repeated bytes reaches in a
+# default process: (LDSU, no TAB, SWZ) needs 1- or 2-byte units without a
+# chunk table (more than 2048 / G phases) in an element of which 64 /
+# gcd(size, 64) fit a tile; the two LDSU = false, TAB = false rows need more
+# than 2048 units in a hull of at most 2048 bytes.  typemap_util.revisiting_types
+# reaches them, pack only.
+TILES_ROWS_REVISITING_ONLY = {(True, False, True), (False, False, True), (False, False, False)}
+
+
+def test_pack_unpack_dispatch_reaches_every_kernel_row(mvx, oracle, types):
+    """mvx_type_last_kernel_symbol over the type lists of this file: in a
+    default process they reach every (LDSU, SWZ, TAB) row of launch_merge and
+    every (LDSU, TAB, SWZ) row of launch_tiles, every unit width (unpack 16,
+    8, 4, 2, 1; tiled pack 8, 4, 2, 1), both k_pack_units table placements,
+    the piece kernel and memcpy -- with the bits checked as everywhere here
+    (typemap_util.roundtrip / pack_only, guard bands included)."""
+    import torch
+    made = TM.whole_word_types(mvx, oracle) + TM.large_types(mvx, oracle) + TM.row_types(mvx, oracle)
+    rev = TM.revisiting_types(mvx, oracle)
+    merge, tiles, units, other = set(), set(), set(), set()
+
+    def note(sym):
+        name, a = TM.parse_symbol(sym)
+        if name == "k_unpack_merge":
+            merge.add((a["W"], a["LDSU"], a["SWZ"], a["TAB"]))
+        elif name == "k_pack_tiles":
+            tiles.add((a["W"], a["LDSU"], a["TAB"], a["SWZ"]))
+        elif name == "k_pack_units":
+            units.add((a["PACK"], a["W"], a["LDS"]))
+        else:
+            other.add(sym)
+    try:
+        for h in made + list(types.values()):
+            for n, phase in ((1, 0), (3, 0), (300, 0), (300, 4)):
+                sp, sp4, su, su4 = TM.roundtrip(mvx, oracle, h, n, phase, seed=h)
+                for s in (sp, sp4, su, su4):
+                    note(s)
+                # a packed buffer 4 bytes off takes neither tile kernel
+                assert not sp4.startswith("k_pack_tiles") and not su4.startswith("k_unpack_merge"), (sp4, su4)
+        tiles_plain = {r[1:] for r in tiles}
+        for h, offs in rev:
+            for n, phase in ((1, 0), (3, 4), (67, 0), (300, 0)):
+                for s in TM.pack_only(mvx, h, offs, n, phase, seed=h):
+                    note(s)
+        x = torch.arange(64, dtype=torch.uint8, device="cuda")
+        y = torch.zeros(64, dtype=torch.uint8, device="cuda")
+        assert mvx.type_pack(F, x, y, 16) == 0 and torch.equal(x, y)
+        note(mvx.type_last_kernel_symbol())
+    finally:
+        TM.free_all(mvx, oracle, made + [h for h, _ in rev])
+    assert {r[1:] for r in merge} == MERGE_ROWS, sorted(merge)
+    assert {r[0] for r in merge} == {16, 8, 4, 2, 1}, sorted(merge)
+    assert {r[1:] for r in tiles} == TILES_ROWS, sorted(tiles)
+    assert TILES_ROWS - tiles_plain == TILES_ROWS_REVISITING_ONLY, sorted(tiles)
+    assert {r[0] for r in tiles} == {8, 4, 2, 1}, sorted(tiles)
+    # the swizzle: picked for 4-byte units ({int; hole; double}) and for 1-byte
+    # ones ({char; hole; int}); the tiled pack takes it for 1- and 2-byte units only
+    assert {r[0] for r in merge if r[2]} >= {4, 1}, sorted(merge)
+    assert {1} <= {r[0] for r in tiles if r[3]} <= {1, 2}, sorted(tiles)
+    # the unit kernel, both ways, table in LDS and (more than 2048 units) in global memory
+    assert {(True, 16, True), (False, 4, True), (True, 4, True), (True, 4, False)} <= units, sorted(units)
+    assert {"k_pack<true>", "k_pack<false>", "memcpy"} <= other, sorted(other)
