@@ -1,5 +1,6 @@
-// mvx_dtype.h -- internal interface of the datatype engine (mvx_dtype.hip)
-// to the op kernels (mvx_ops.hip), both in libmvx_hip.so.  The C-ABI is in
+// mvx_dtype.h -- internal interfaces of the datatype engine (mvx_dtype.hip,
+// host code only) inside libmvx_hip.so: to the op kernels (mvx_ops.hip) and
+// to the device pack / unpack path (mvx_pack.hip).  The C-ABI is in
 // include/mvx_hip.h.
 #ifndef MVX_DTYPE_INTERNAL_H
 #define MVX_DTYPE_INTERNAL_H
@@ -27,6 +28,26 @@ struct Info {
 
 // basic or derived handle; false for an unknown handle
 bool info(int handle, Info *out);
+
+// ---- to the pack / unpack path (mvx_pack.hip) -----------------------------
+struct Blk { long off, len; };      // one block of a type map
+struct PackCache;                   // a derived type's device side, defined in mvx_pack.hip
+
+struct PackView {
+    long extent, size, nblk;    // nblk: blocks of one element's map, in order, merged
+    const Blk *map;             // derived handles: the blocks, valid while the type lives
+    PackCache **cache;          // derived handles: where the type keeps its cache (null
+                                // until its first pack or unpack); basic handles: null
+};
+#pragma GCC visibility push(hidden)     // libmvx_hip.so exports none of these
+// basic or derived handle; false for an unknown handle
+bool pack_view(int handle, PackView *out);
+// the hull of a map: its lowest byte and one past its highest (0, 0 if empty)
+void hull(const Blk *map, long nblk, long *lo, long *hi);
+// mvx_pack.hip: frees a cache, device memory included, when its type is freed
+// (the type engine's one touch of the device)
+void pack_cache_free(PackCache *c);
+#pragma GCC visibility pop
 
 }  // namespace dt
 }  // namespace mvx

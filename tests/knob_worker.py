@@ -10,7 +10,7 @@ Runs small launches (tests/small_launch.py) or pack / unpack round trips
 (tests/typemap_util.py), each compared with the CPU oracle bit for bit, and
 checks the kernel the dispatch reports against what the knobs select
 (mvx_op_program / launch in mvx_ops.hip, kfam in mvx_ops_kern.h, pack in
-mvx_dtype.hip).  Prints one line per check and, last, `knobs ok <n> checks`;
+mvx_pack.hip).  Prints one line per check and, last, `knobs ok <n> checks`;
 any failure is an uncaught exception (non-zero exit).
 
 Knobs that would hide one another sit in different groups: MVX_NO_BODY would

@@ -1,6 +1,6 @@
 """GPU: every kernel-selecting environment knob, each group in a fresh process.
 
-mvx_ops.hip, mvx_ops_kern.h and mvx_dtype.hip read their knobs once into
+mvx_ops.hip, mvx_ops_kern.h and mvx_pack.hip read their knobs once into
 statics, so a knob can only be tested in a process that starts with it set.
 tests/knob_worker.py holds the groups (its ENV) and the checks; here one
 worker runs at a time, each under its own time limit, with the parent's

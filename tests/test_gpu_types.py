@@ -312,7 +312,7 @@ def test_whole_word_unpack_keeps_every_other_byte(mvx, oracle):
     """Pack through LDS tiles (k_pack_tiles, into a 16-byte-aligned packed
     buffer) gives the unit kernel's stream (into a buffer 4 bytes off).
     Unpack of types whose maps leave holes inside 64-byte sectors runs by
-    whole 16-byte words (mvx_dtype.hip k_unpack_merge: each tile read into
+    whole 16-byte words (mvx_pack.hip k_unpack_merge: each tile read into
     LDS, the units merged in, written back whole).  Against the oracle's
     type-map copy over a patterned buffer with guard bands: type-map bytes
     land, holes and guards keep their pattern -- at counts 1, 2, 3, 1000
@@ -445,8 +445,34 @@ def test_whole_word_unpack_of_large_elements(mvx, oracle):
             oracle.type_free(h)
 
 
+def test_reused_handle_gets_its_own_unit_tables(mvx, oracle):
+    """The device side of a type (unit tables, reach, whole-word decision)
+    goes with the type when it is freed: "every other float" runs its 4-byte
+    unit kernels, is freed, and struct {char; hole; int} -- size 5, so 1-byte
+    units or the piece kernel only -- built into the same handle must not
+    meet the float type's tables.  The bits are checked by the round trip."""
+    h = TM.both(mvx, oracle, "vector", 2, 1, 2, F)
+    try:
+        widths = {TM.parse_symbol(s)[1].get("W") for s in TM.roundtrip(mvx, oracle, h, 3, 0)}
+        assert widths == {4}, widths
+    finally:
+        TM.free_all(mvx, oracle, [h])
+    h2 = TM.both(mvx, oracle, "struct", 2, [1, 1], [0, 4], [C, I])
+    try:
+        assert h2 == h
+        for phase in (0, 4):
+            syms = TM.roundtrip(mvx, oracle, h2, 3, phase)
+            for s in syms:
+                name, a = TM.parse_symbol(s)
+                assert a["W"] == 1 if a else name == "k_pack", (phase, syms)
+            # the aligned pack and unpack did take unit tables
+            assert TM.parse_symbol(syms[0])[1] and TM.parse_symbol(syms[2])[1], (phase, syms)
+    finally:
+        TM.free_all(mvx, oracle, [h2])
+
+
 # launch_merge's rows (LDSU, SWZ, TAB) and launch_tiles' rows (LDSU, TAB, SWZ),
-# mvx_dtype.hip; every one is reached below
+# mvx_pack.hip; every one is reached below
 MERGE_ROWS = {(False, True, True), (False, False, True), (False, True, False), (False, False, False),
               (True, True, False), (True, False, False)}
 TILES_ROWS = {(False, True, True), (False, True, False), (True, False, True), (True, False, False),

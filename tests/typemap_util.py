@@ -53,7 +53,7 @@ def large_types(mvx, oracle):
 
 def row_types(mvx, oracle):
     """Types that reach what the two lists above leave out of launch_merge's
-    and launch_tiles' kernel choice (mvx_dtype.hip)."""
+    and launch_tiles' kernel choice (mvx_pack.hip)."""
     return [
         both(mvx, oracle, "hvector", 2, 2, 32, D),            # 16 B of every 32: 16-byte units
         # 3 chars of every 4, 2100 units in 2799 bytes: offsets from global
