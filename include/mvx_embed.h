@@ -24,6 +24,15 @@ extern "C" {
 
 #define MVX_UNIQUE_ID_BYTES 128
 
+/* EXTENSION beyond the reference ABI: the 16-bit floating datatypes
+ * (include/mvx_mpi.h has the same block and their semantics).  The host MPI
+ * has no handle for them, so the MVAPICH shim never passes them; a caller of
+ * mvx_coll_* names them directly. */
+#ifndef MVX_FLOAT16
+#define MVX_FLOAT16            64   /* IEEE binary16 */
+#define MVX_BFLOAT16           65   /* the upper 16 bits of a binary32 */
+#endif
+
 /* communicators: one process per GPU, collective over `size` processes.
  * Creation and every call on a communicator run on its device and leave the
  * caller's current device as it was. */

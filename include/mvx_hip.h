@@ -44,7 +44,9 @@ extern "C" {
 /* Largest k one combine launch takes. */
 #define MVX_COMBINE_KMAX 8
 
-/* 1 if a device kernel exists for (op, dtype); 0 otherwise. */
+/* 1 if a device kernel exists for (op, dtype); 0 otherwise.  dtype is a
+ * reference handle, a derived one, or one of the extension types
+ * MVX_FLOAT16 / MVX_BFLOAT16 (mvx_mpi.h), which have MPI_FLOAT's seven ops. */
 int mvx_op_supported(int op, int dtype);
 /* Bytes of one element as the (op, dtype) kernel reads it (the C pair
  * struct for MAXLOC / MINLOC on a struct type), or 0 if undefined. */

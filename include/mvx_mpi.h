@@ -79,6 +79,19 @@ typedef long MPI_Aint;      /* x86-64 LP64, the reference build's address int */
 #define MPI_CHARACTER          ((MPI_Datatype)1)
 #define MPI_UNSIGNED_LONG_LONG ((MPI_Datatype)35)
 
+/* EXTENSION beyond the reference ABI: 16-bit floating types.  The reference's
+ * MPI-1 has no handle for them; these take values in the free range above
+ * its last handle (35).  Extent, size and alignment 2.  The ops are those of
+ * MPI_FLOAT (MAX, MIN, SUM, PROD, LAND, LOR, LXOR), computed as global_ops.c
+ * would for one more C floating type: every step correctly rounded
+ * (round-to-nearest-even) in the 16-bit format, subnormals kept, MAX / MIN
+ * as the selects of coll.h:14-19.  Also defined, with
+ * the same values, in mvx_embed.h. */
+#ifndef MVX_FLOAT16
+#define MVX_FLOAT16            64   /* IEEE binary16 */
+#define MVX_BFLOAT16           65   /* the upper 16 bits of a binary32 */
+#endif
+
 /* Ops: reference include/mpi.h:127-140 */
 #define MPI_OP_NULL ((MPI_Op)0)
 #define MPI_MAX     ((MPI_Op)100)

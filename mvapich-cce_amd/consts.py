@@ -17,6 +17,8 @@ MPI_LOGICAL, MPI_REAL, MPI_DOUBLE_PRECISION, MPI_INTEGER = 25, 26, 27, 28
 MPI_2INTEGER, MPI_2COMPLEX, MPI_2DOUBLE_COMPLEX, MPI_2REAL, MPI_2DOUBLE_PRECISION = 29, 30, 31, 32, 33
 MPI_CHARACTER = 1
 MPI_UNSIGNED_LONG_LONG = 35
+# EXTENSION beyond the reference ABI (include/mvx_mpi.h): the 16-bit floats
+MVX_FLOAT16, MVX_BFLOAT16 = 64, 65
 
 MPI_OP_NULL = 0
 MPI_MAX, MPI_MIN, MPI_SUM, MPI_PROD, MPI_LAND, MPI_BAND = 100, 101, 102, 103, 104, 105
@@ -62,6 +64,8 @@ NP_DTYPE = {
     MPI_LOGICAL: np.dtype(np.int32), MPI_REAL: np.dtype(np.float32), MPI_DOUBLE_PRECISION: np.dtype(np.float64),
     MPI_INTEGER: np.dtype(np.int32), MPI_2INTEGER: PAIR_2INT, MPI_2REAL: PAIR_2REAL,
     MPI_2DOUBLE_PRECISION: PAIR_2DOUBLE, MPI_2COMPLEX: PAIR_2COMPLEX, MPI_2DOUBLE_COMPLEX: PAIR_2DCOMPLEX,
+    # numpy has no bfloat16: its elements are uint16 bit patterns
+    MVX_FLOAT16: np.dtype(np.float16), MVX_BFLOAT16: np.dtype(np.uint16),
 }
 
 OP_NAMES = {MPI_MAX: "MPI_MAX", MPI_MIN: "MPI_MIN", MPI_SUM: "MPI_SUM", MPI_PROD: "MPI_PROD",
@@ -77,7 +81,8 @@ TYPE_NAMES = {MPI_CHAR: "MPI_CHAR", MPI_UNSIGNED_CHAR: "MPI_UNSIGNED_CHAR", MPI_
               MPI_DOUBLE_COMPLEX: "MPI_DOUBLE_COMPLEX", MPI_LOGICAL: "MPI_LOGICAL", MPI_REAL: "MPI_REAL",
               MPI_DOUBLE_PRECISION: "MPI_DOUBLE_PRECISION", MPI_INTEGER: "MPI_INTEGER",
               MPI_2INTEGER: "MPI_2INTEGER", MPI_2COMPLEX: "MPI_2COMPLEX", MPI_2DOUBLE_COMPLEX: "MPI_2DOUBLE_COMPLEX",
-              MPI_2REAL: "MPI_2REAL", MPI_2DOUBLE_PRECISION: "MPI_2DOUBLE_PRECISION"}
+              MPI_2REAL: "MPI_2REAL", MPI_2DOUBLE_PRECISION: "MPI_2DOUBLE_PRECISION",
+              MVX_FLOAT16: "MVX_FLOAT16", MVX_BFLOAT16: "MVX_BFLOAT16"}
 
 # (op, type) pairs the reference defines (global_ops.c)
 _INTS = [MPI_CHAR, MPI_UNSIGNED_CHAR, MPI_SHORT, MPI_UNSIGNED_SHORT, MPI_INT, MPI_UNSIGNED, MPI_LONG,
@@ -95,6 +100,9 @@ DEFINED = {
     MPI_BXOR: _INTS + [MPI_BYTE, MPI_LOGICAL],
     MPI_MAXLOC: _PAIRS, MPI_MINLOC: _PAIRS,
 }
+# the extension types: the seven ops of MPI_FLOAT (DEFINED stays the reference's table)
+_HALFS = [MVX_FLOAT16, MVX_BFLOAT16]
+DEFINED_EXT = {op: list(_HALFS) for op in (MPI_MAX, MPI_MIN, MPI_SUM, MPI_PROD, MPI_LAND, MPI_LOR, MPI_LXOR)}
 DEVICE_TYPES = sorted(NP_DTYPE)
 
 # mvx_comm_set_call_kinds (include/mvx_embed.h)

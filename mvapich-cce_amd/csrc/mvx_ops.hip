@@ -1,7 +1,7 @@
 // mvx_ops.hip -- the device side of the MPI local reduction path, written for
 // gfx950 (CDNA4, wave64): the (op, datatype) dispatch, the launch policy and
 // the C-ABI of include/mvx_hip.h.  The kernels and their per-op tables are in
-// mvx_ops_kern.h and mvx_ops_{cmp,arith,logic,loc}.hip (design notes at the
+// mvx_ops_kern.h and mvx_ops_{cmp,arith,logic,loc,half}.hip (design notes at the
 // top of mvx_ops_kern.h).
 #include "mvx_ops_kern.h"
 
@@ -82,6 +82,8 @@ static int ekind(int dtype)
     case MPI_REAL: return EK_F32;
     case MPI_DOUBLE_PRECISION: return EK_F64;
     case MPI_LOGICAL: return EK_LOGICAL;
+    case MVX_FLOAT16: return EK_F16;          // extension (mvx_mpi.h)
+    case MVX_BFLOAT16: return EK_BF16;
     // the Fortran pairs: contiguous(2, x), the MAXLOC / MINLOC stride-2 case
     // of x's dte_type (global_ops.c:1387-1503); no case for COMPLEX (1498)
     case MPI_2INTEGER: return EK_PII;
@@ -102,6 +104,10 @@ static const KSet *lookup(int op, int dtype, int *rc)
     *rc = MVX_ERR_OP_NOT_DEFINED;
     if (ek == EK_LOGICAL && (op == MPI_BAND || op == MPI_BOR || op == MPI_BXOR))
         ek = EK_U32;                 // bitwise on the MPI_Fint word
+    if (ek == EK_F16 || ek == EK_BF16) {
+        if (op < MPI_MAX || op > MPI_MAXLOC) *rc = MPI_ERR_OP;
+        return lookup_half(op, ek);
+    }
 
     switch (op) {
     case MPI_MAX: case MPI_MIN:

@@ -1,7 +1,7 @@
 #pragma once
 // mvx_ops_kern.h -- kernels and kernel sets of the device side of the MPI local
 // reduction path (included by mvx_ops.hip and the per-op table units
-// mvx_ops_{cmp,arith,logic,loc}.hip, compiled in parallel), written for
+// mvx_ops_{cmp,arith,logic,loc,half}.hip, compiled in parallel), written for
 // gfx950 (CDNA4, wave64).  Built into libmvx_hip.so; C-ABI in
 // include/mvx_hip.h.
 //
@@ -195,6 +195,56 @@ __device__ __forceinline__ pp<xf80> xloc2(pp<xf80> a, pp<xf80> b)
 template <> struct F<OMAXLOC, pp<xf80>> { static __device__ __forceinline__ pp<xf80> f(pp<xf80> a, pp<xf80> b) { return xloc2<false>(a, b); } };
 template <> struct F<OMINLOC, pp<xf80>> { static __device__ __forceinline__ pp<xf80> f(pp<xf80> a, pp<xf80> b) { return xloc2<true>(a, b); } };
 
+// EXTENSION beyond the reference: the 16-bit floating types MVX_FLOAT16 and
+// MVX_BFLOAT16 (include/mvx_mpi.h), treated as global_ops.c would treat one
+// more C floating type next to float and double.  f16 is the compiler's IEEE
+// binary16 and takes the generic ops above: every step is one correctly
+// rounded half-precision instruction, subnormals kept.  bf16 is the upper
+// half of a binary32: widened exactly by a shift, combined in f32 and
+// narrowed round-to-nearest-even by the __bf16 conversion -- a sum or a
+// product of two bf16 values rounded to f32 and then to bf16 equals the
+// directly rounded one (24 >= 2 * 8 + 2; the product is exact in f32).  No
+// step's f32 value is carried into the next.  MAX / MIN compare the widened
+// values and keep the chosen operand's 16 bits; the logical ops store 1.0
+// (0x3F80) or 0.
+typedef _Float16 f16;
+struct bf16 { uint16_t u; };
+static_assert(sizeof(f16) == 2 && sizeof(bf16) == 2, "");
+
+__device__ __forceinline__ float bits_f32(uint32_t w)
+{
+    float f;
+    __builtin_memcpy(&f, &w, 4);
+    return f;
+}
+__device__ __forceinline__ bf16 bf_narrow(float f)
+{
+    const __bf16 h = (__bf16)f;
+    bf16 r;
+    __builtin_memcpy(&r.u, &h, 2);
+    return r;
+}
+template <int O>
+__device__ __forceinline__ bf16 bf_op(bf16 a, bf16 b)
+{
+    const float x = bits_f32((uint32_t)a.u << 16), y = bits_f32((uint32_t)b.u << 16);
+    bf16 t;
+    if constexpr (O == OMAX) return (y > x) ? b : a;
+    else if constexpr (O == OMIN) return (x > y) ? b : a;
+    else if constexpr (O == OSUM) return bf_narrow(x + y);
+    else if constexpr (O == OPROD) return bf_narrow(x * y);
+    else if constexpr (O == OLAND) { t.u = (x != 0.0f && y != 0.0f) ? 0x3f80 : 0; return t; }
+    else if constexpr (O == OLOR) { t.u = (x != 0.0f || y != 0.0f) ? 0x3f80 : 0; return t; }
+    else { static_assert(O == OLXOR, ""); t.u = ((x != 0.0f) != (y != 0.0f)) ? 0x3f80 : 0; return t; }
+}
+#define MVX_BF16_OP(O)                                                        \
+    template <> struct F<O, bf16> {                                           \
+        static __device__ __forceinline__ bf16 f(bf16 a, bf16 b) { return bf_op<O>(a, b); } \
+    };
+MVX_BF16_OP(OMAX) MVX_BF16_OP(OMIN) MVX_BF16_OP(OSUM) MVX_BF16_OP(OPROD)
+MVX_BF16_OP(OLAND) MVX_BF16_OP(OLOR) MVX_BF16_OP(OLXOR)
+#undef MVX_BF16_OP
+
 #ifdef MVX_OPS_LOGICAL_TU   // one TU owns the .TRUE. / .FALSE. words (mvx_ops_logic.hip)
 // MPI_LOGICAL (dte_type MPIR_LOGICAL, one MPI_Fint): LAND / LOR / LXOR
 // compare each word with the Fortran .TRUE. and store .TRUE. or .FALSE.
@@ -323,6 +373,81 @@ template <int O> struct CF<O, uint8_t> {
 };
 template <int O> struct CF<O, int8_t> {
     static __device__ __forceinline__ void f(Chunk<int8_t> &a, const Chunk<int8_t> &b) { CF8<O, true>::f(a, b); }
+};
+
+// The 16-bit floating types stay in their four 32-bit words too, two elements
+// a word: W16<O, T>::f is the op on one word.
+template <> struct Chunk<f16> { uint32_t w[4]; };
+template <> struct Chunk<bf16> { uint32_t w[4]; };
+
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+template <int O, typename T> struct W16;
+
+// f16: SUM / PROD are one packed instruction (v_pk_add_f16 / v_pk_mul_f16);
+// MAX / MIN are a compare and a select per half, not v_pk_max / v_pk_min,
+// whose NaN and signed-zero results are not the select's.
+template <int O> struct W16<O, f16> {
+    static __device__ __forceinline__ uint32_t f(uint32_t a, uint32_t b)
+    {
+        f16x2 x, y, r;
+        __builtin_memcpy(&x, &a, 4);
+        __builtin_memcpy(&y, &b, 4);
+        if constexpr (O == OSUM) r = x + y;
+        else if constexpr (O == OPROD) r = x * y;
+        else { r.x = F<O, f16>::f(x.x, y.x); r.y = F<O, f16>::f(x.y, y.y); }
+        uint32_t w;
+        __builtin_memcpy(&w, &r, 4);
+        return w;
+    }
+};
+
+// bf16: the low half widens by a shift, the high half by a mask; SUM / PROD
+// narrow both f32 results with one packed conversion (v_cvt_pk_bf16_f32);
+// MAX / MIN select the original halves.
+template <int O> struct W16<O, bf16> {
+    static __device__ __forceinline__ uint32_t f(uint32_t a, uint32_t b)
+    {
+        const float xl = bits_f32(a << 16), xh = bits_f32(a & 0xffff0000u);
+        const float yl = bits_f32(b << 16), yh = bits_f32(b & 0xffff0000u);
+        if constexpr (O == OMAX || O == OMIN) {
+            const bool tl = O == OMAX ? (yl > xl) : (xl > yl);
+            const bool th = O == OMAX ? (yh > xh) : (xh > yh);
+            return ((tl ? b : a) & 0xffffu) | ((th ? b : a) & 0xffff0000u);
+        } else if constexpr (O == OSUM || O == OPROD) {
+            f32x2 r;
+            r.x = O == OSUM ? xl + yl : xl * yl;
+            r.y = O == OSUM ? xh + yh : xh * yh;
+            const bf16x2 h = __builtin_convertvector(r, bf16x2);
+            uint32_t w;
+            __builtin_memcpy(&w, &h, 4);
+            return w;
+        } else {
+            const bool al = xl != 0.0f, ah = xh != 0.0f, bl = yl != 0.0f, bh = yh != 0.0f;
+            bool tl, th;
+            if constexpr (O == OLAND) { tl = al && bl; th = ah && bh; }
+            else if constexpr (O == OLOR) { tl = al || bl; th = ah || bh; }
+            else { static_assert(O == OLXOR, ""); tl = al != bl; th = ah != bh; }
+            return (tl ? 0x3f80u : 0u) | (th ? 0x3f800000u : 0u);
+        }
+    }
+};
+
+template <int O, typename T>
+struct CF16 {
+    static __device__ __forceinline__ void f(Chunk<T> &a, const Chunk<T> &b)
+    {
+#pragma unroll
+        for (int w = 0; w < 4; ++w) a.w[w] = W16<O, T>::f(a.w[w], b.w[w]);
+    }
+};
+template <int O> struct CF<O, f16> {
+    static __device__ __forceinline__ void f(Chunk<f16> &a, const Chunk<f16> &b) { CF16<O, f16>::f(a, b); }
+};
+template <int O> struct CF<O, bf16> {
+    static __device__ __forceinline__ void f(Chunk<bf16> &a, const Chunk<bf16> &b) { CF16<O, bf16>::f(a, b); }
 };
 
 // whole-element store: the pair padding is an explicit member carried from
@@ -914,7 +1039,9 @@ enum { EK_NONE = 0, EK_I8, EK_U8, EK_BYTE, EK_I16, EK_U16, EK_I32, EK_U32,
        EK_PSI, EK_PII, EK_LDBL, EK_LDBL_INT,
        // derived contiguous types: count-2 pairs of one base, and the rest
        EK_PP8, EK_PP16, EK_PP64, EK_PPF, EK_PPD, EK_PPX, EK_DERIVED,
-       EK_LOGICAL };
+       EK_LOGICAL,
+       // extension: MVX_FLOAT16, MVX_BFLOAT16
+       EK_F16, EK_BF16 };
 
 // Integer SUM/PROD/logical/bitwise results do not depend on signedness in
 // two's complement, so those share the unsigned kernel of the same width;
@@ -927,6 +1054,9 @@ enum { EK_NONE = 0, EK_I8, EK_U8, EK_BYTE, EK_I16, EK_U16, EK_I32, EK_U32,
 #define FLOATS(O, NAME)                                                      \
     case EK_F32: { static KSet s = kset<O, float>(NAME "_f32"); return &s; } \
     case EK_F64: { static KSet s = kset<O, double>(NAME "_f64"); return &s; }
+#define HALFS(O, NAME)                                                       \
+    case EK_F16:  { static KSet s = kset<O, f16>(NAME "_f16"); return &s; }  \
+    case EK_BF16: { static KSet s = kset<O, bf16>(NAME "_bf16"); return &s; }
 #define CMPLX(O, NAME)                                                       \
     case EK_C32: { static KSet s = kset<O, cf32>(NAME "_c32"); return &s; }  \
     case EK_C64: { static KSet s = kset<O, cf64>(NAME "_c64"); return &s; }
@@ -967,6 +1097,7 @@ const KSet *lookup_arith(int op, int ek);   // SUM, PROD          mvx_ops_arith.
 const KSet *lookup_logic(int op, int ek);   // L* and B* ops      mvx_ops_logic.hip
 int flog_sync();                            // MPI_LOGICAL's words on this device (mvx_ops_logic.hip)
 const KSet *lookup_loc(int op, int ek);     // MAXLOC, MINLOC     mvx_ops_loc.hip
+const KSet *lookup_half(int op, int ek);    // every op on the 16-bit floats  mvx_ops_half.hip
 
 }  // namespace mvx
 

@@ -13,6 +13,9 @@ operand is served from the 256 MiB Infinity Cache:
 
 Prints one JSON line per config: algorithmic bytes, kernel time (HIP events on
 the launch stream), GB/s and fraction of the 8 TB/s HBM peak.
+
+Modes (arguments): sweep, all, all-tree, ks, x87 add lines to the four
+configs; half runs only the 16-bit floating types against MPI_SHORT.
 """
 import importlib
 import json
@@ -89,8 +92,22 @@ def _x87_values(x, dtype, mvx):
     return x
 
 
+def half(mvx):
+    """The 16-bit floating extension types next to MPI_SHORT (the sum_u16 /
+    max_i16 kernels): the apply kernel at 256 MiB vectors and the 8-leaf tree
+    at 32 MiB leaves, SUM and MAX.  The three types move the same bytes at
+    the same element width, so the lines differ by the arithmetic alone."""
+    for t, tn in ((mvx.MVX_FLOAT16, "f16"), (mvx.MVX_BFLOAT16, "bf16"), (mvx.MPI_SHORT, "short")):
+        for op, on in ((mvx.MPI_SUM, "sum"), (mvx.MPI_MAX, "max")):
+            run(mvx, "H2-%s-%s" % (on, tn), op, t, 2, 1, 256 * MIB, 4, reps=10, warm=2)
+            run(mvx, "H8-%s-%s" % (on, tn), op, t, 8, 0, 32 * MIB, 4, reps=10, warm=2)
+
+
 def main():
     mvx = importlib.import_module("mvapich-cce_amd")
+    if "half" in sys.argv[1:]:      # on its own: the BASELINE configs are not repeated
+        half(mvx)
+        return
     run(mvx, "C2", mvx.MPI_SUM, mvx.MPI_FLOAT, 2, 1, 256 * MIB, 4)
     run(mvx, "C3", mvx.MPI_SUM, mvx.MPI_FLOAT, 8, 0, 32 * MIB, 4)
     run(mvx, "C4", mvx.MPI_BAND, mvx.MPI_LONG, 4, 1, 256 * MIB, 2)
