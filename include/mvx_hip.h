@@ -161,6 +161,24 @@ int mvx_op_program(int op, int dtype, const void *const *srcs,
 unsigned mvx_tree_mask(int k);
 unsigned mvx_chain_mask(int k);
 
+/* What mvx_op_program would launch for these arguments, without launching:
+ * the same checks and return codes, then the kernel template as rocprofv3
+ * names it, the short tag, the grid and the dynamic LDS reservation.  Only
+ * the addresses' alignment is looked at (no buffer is read, so any address
+ * will do), no device is needed, and mvx_hip_last_* keep their values.
+ * n == 0: MPI_SUCCESS with blocks 0 and an empty symbol.  The plain op
+ * mvx_op_apply(in, inout) is k = 2, srcs = {inout, in}, tree_mask 1,
+ * dst = inout. */
+struct mvx_launch_plan {
+    const char *symbol;    /* static storage */
+    char tag[96];
+    unsigned blocks;
+    size_t dynamic_lds;
+};
+int mvx_op_plan(int op, int dtype, const void *const *srcs, const void *const *fold, int k,
+                unsigned tree_mask, unsigned chain_mask, const void *dst, size_t n,
+                struct mvx_launch_plan *out);
+
 /* Launch knobs (0 = keep): grid cap in blocks; non-temporal threshold as
  * log2(bytes touched per launch), -1 = never.  Env: MVX_BLOCK_CAP,
  * MVX_NT_MIN_BYTES.  Defaults: one-pass grid, non-temporal from 64 MiB. */

@@ -116,6 +116,7 @@ def _load():
     _hip.mvx_op_apply.argtypes = [i, i, vp, vp, sz, vp]
     _hip.mvx_op_combine.argtypes = [i, i, pvp, pvp, i, i, vp, sz, vp]
     _hip.mvx_op_program.argtypes = [i, i, pvp, pvp, i, ctypes.c_uint, ctypes.c_uint, vp, sz, vp]
+    _hip.mvx_op_plan.argtypes = [i, i, pvp, pvp, i, ctypes.c_uint, ctypes.c_uint, vp, sz, vp]
     _hip.mvx_tree_mask.argtypes = [i]
     _hip.mvx_tree_mask.restype = ctypes.c_uint
     _hip.mvx_chain_mask.argtypes = [i]

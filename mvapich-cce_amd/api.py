@@ -10,7 +10,7 @@ from . import coll, hip
 from .consts import COLL_ALLREDUCE, COLL_REDUCE, COLL_REDUCE_SCATTER  # noqa: F401
 
 __all__ = [
-    "addr", "stream_handle", "op_apply", "op_combine", "op_program", "Comm",
+    "addr", "stream_handle", "op_apply", "op_combine", "op_program", "op_plan", "LaunchPlan", "Comm",
     "MPI_Allreduce", "MPI_Reduce", "MPI_Reduce_scatter", "MPI_Scan", "MPI_Op_create", "MPI_Op_free", "op_create_device",
     "MPIR_call", "op_errno", "last_kernel", "last_kernel_symbol", "last_launch", "set_launch",
     "set_fortran_logical", "comm_reap", "host_register_enable", "host_unregister", "host_register_stats",
@@ -68,6 +68,23 @@ def op_program(op, dtype, srcs, dst, n, tree_mask, chain_mask, folds=None, strea
     fo = _pp(folds) if folds is not None else None
     return hip().mvx_op_program(op, dtype, _pp(srcs), fo, len(srcs), tree_mask, chain_mask, addr(dst), n,
                                 stream_handle(stream))
+
+
+class LaunchPlan(ctypes.Structure):
+    """Mirror of ``mvx_launch_plan`` (include/mvx_hip.h)."""
+    _fields_ = [("symbol", ctypes.c_char_p), ("tag", ctypes.c_char * 96), ("blocks", ctypes.c_uint),
+                ("dynamic_lds", ctypes.c_size_t)]
+
+
+def op_plan(op, dtype, srcs, dst, n, tree_mask, chain_mask, folds=None):
+    """What op_program would launch for these arguments (mvx_op_plan): (rc,
+    LaunchPlan).  Nothing is launched and no buffer is read, so plain integer
+    addresses do; no device is needed."""
+    fo = _pp(folds) if folds is not None else None
+    out = LaunchPlan()
+    rc = hip().mvx_op_plan(op, dtype, _pp(srcs), fo, len(srcs), tree_mask, chain_mask, addr(dst), n,
+                           ctypes.byref(out))
+    return rc, out
 
 
 def set_launch(block_cap=0, nt_min_log2=0):

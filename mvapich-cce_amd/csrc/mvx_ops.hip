@@ -1,9 +1,15 @@
 // mvx_ops.hip -- the device side of the MPI local reduction path, written for
-// gfx950 (CDNA4, wave64): the (op, datatype) dispatch, the launch policy and
-// the C-ABI of include/mvx_hip.h.  The kernels and their per-op tables are in
-// mvx_ops_kern.h and mvx_ops_{cmp,arith,logic,loc,half}.hip (design notes at the
-// top of mvx_ops_kern.h).
-#include "mvx_ops_kern.h"
+// gfx950 (CDNA4, wave64): the (op, datatype) dispatch, the knobs (config), the
+// launch policy and the C-ABI of include/mvx_hip.h.  The policy is three pure
+// host functions -- choose_family, split (the alignment rule) and plan -- that
+// never touch the device or a buffer; run() is the one place that launches.
+// mvx_op_plan answers with the plan alone.  The kernels are in mvx_ops_kern.h
+// (design notes at its top), their host-side tables in mvx_ops_tab.h and
+// mvx_ops_{cmp,arith,logic,loc,half}.hip.
+#include <stdlib.h>
+
+#include "mvx_dtype.h"
+#include "mvx_ops_tab.h"
 
 namespace mvx {
 
@@ -125,27 +131,39 @@ static const KSet *lookup(int op, int dtype, int *rc)
     }
 }
 
-// Grid: one pass over the data (a block per 256*U chunks) up to this cap,
-// grid-stride beyond it; a full pass measured best on the config-2 kernel.
-static int g_block_cap = 1 << 20;
-// Non-temporal above this many bytes touched by one launch (all operands +
-// the result); below it the result is likely re-read from L2 / MALL.
-static long g_nt_min_bytes = 64L << 20;
-static int g_prog4 = 1;          // programs over 3-4 leaves on the KMAX = 4 kernels
-static int g_prog_u = 1;
-static int g_generic_only = 0;   // MVX_PROG_GENERIC=1: no fixed-tree kernels (A/B runs)
-static int g_chain_rt = 1;       // MVX_CHAIN_RT=0: chains of 5-7 leaves on the masked program (A/B)
-// resident blocks per CU for the non-temporal launches of each family (0 =
-// as many as registers allow); MVX_CAP_{APPLY,PROG,TREE} override for A/B runs
-static int g_cap[FAM_N] = {0, 0, 2};
-static int g_no_body = 0;        // MVX_NO_BODY=1: fixed trees through k_combine (A/B runs)
-static size_t g_cap_lds[FAM_N];
-static const char *g_last = "";
-static char g_last_buf[96];
-static const char *g_last_sym = "";
-static unsigned g_last_blocks;
-static size_t g_last_lds;
-static const void *g_last_fn;
+// The knobs (Config, mvx_ops_tab.h) by name.  A value counts when the rule
+// says so: '*' any, '+' only a positive one, '=' only `v` itself.
+static Config g_cfg;
+static const struct { const char *name; long Config::*field; char rule; long v; } KNOBS[] = {
+    {"MVX_NT_MIN_BYTES", &Config::nt_min_bytes, '*', 0},
+    {"MVX_BLOCK_CAP", &Config::block_cap, '+', 0},
+    {"MVX_PROG_U", &Config::prog_u, '=', 2},
+    {"MVX_PROG_GENERIC", &Config::generic_only, '=', 1},
+    {"MVX_PROG4", &Config::prog4, '=', 0},
+    {"MVX_CHAIN_RT", &Config::chain_rt, '=', 0},
+    {"MVX_NO_BODY", &Config::no_body, '=', 1},
+    {"MVX_CAP_APPLY", &Config::cap_apply, '*', 0},
+    {"MVX_CAP_PROG", &Config::cap_prog, '*', 0},
+    {"MVX_CAP_TREE", &Config::cap_tree, '*', 0},
+    {"MVX_PXI_U", &Config::pxi_u, '*', 0},
+    {"MVX_PXI_CAP", &Config::pxi_cap, '*', 0},
+    {"MVX_PXI_APPLY_CAP", &Config::pxi_apply_cap, '*', 0},
+};
+
+const Config &config()
+{
+    static bool done = false;
+    if (done) return g_cfg;
+    done = true;
+    for (const auto &kn : KNOBS) {
+        const char *e = getenv(kn.name);
+        if (!e) continue;
+        // the byte threshold is a long; every other knob is read as an int
+        const long v = kn.field == &Config::nt_min_bytes ? atol(e) : (long)atoi(e);
+        if (kn.rule == '*' || (kn.rule == '+' && v > 0) || (kn.rule == '=' && v == kn.v)) g_cfg.*kn.field = v;
+    }
+    return g_cfg;
+}
 
 // LDS per CU of the device the kernels run on, from its architecture name
 // (the runtime's per-multiprocessor attribute reports the 64 KiB per-block
@@ -179,43 +197,36 @@ static size_t cap_lds(int cap)
     return b > 64 * 1024 ? 64 * 1024 : b;
 }
 
-static void init_env()
+// ---------------------------------------------------------------------------
+// the launch policy: which template runs, with how many blocks and which LDS
+// reservation.  Pure host arithmetic on addresses and sizes.
+
+// The kernel family of a program over k leaves (k <= 2: the plain op).
+static const KFam &choose_family(const KSet *ks, const Config &cfg, int k, unsigned tree_mask,
+                                 unsigned chain_mask, bool folded)
 {
-    static int done = 0;
-    if (done) return;
-    done = 1;
-    const char *e = getenv("MVX_NT_MIN_BYTES");
-    if (e) g_nt_min_bytes = atol(e);
-    e = getenv("MVX_BLOCK_CAP");
-    if (e && atoi(e) > 0) g_block_cap = atoi(e);
-    e = getenv("MVX_PROG_U");
-    if (e && atoi(e) == 2) g_prog_u = 2;
-    e = getenv("MVX_PROG_GENERIC");
-    if (e && atoi(e) == 1) g_generic_only = 1;
-    e = getenv("MVX_PROG4");
-    if (e && atoi(e) == 0) g_prog4 = 0;
-    e = getenv("MVX_CHAIN_RT");
-    if (e && atoi(e) == 0) g_chain_rt = 0;
-    e = getenv("MVX_NO_BODY");
-    if (e && atoi(e) == 1) g_no_body = 1;
-    const char *caps[FAM_N] = {"MVX_CAP_APPLY", "MVX_CAP_PROG", "MVX_CAP_TREE"};
-    for (int f = 0; f < FAM_N; ++f) {
-        e = getenv(caps[f]);
-        if (e) g_cap[f] = atoi(e);
-        g_cap_lds[f] = cap_lds(g_cap[f]);
-    }
+    if (k <= 2) return ks->apply;
+    const bool fixed = !cfg.generic_only && !folded;
+    if (fixed && chain_mask == 0 && (k == 8 || k == 4) && tree_mask == mvx_tree_mask(k))
+        return k == 8 ? ks->tree8 : ks->tree4;
+    /* chains of 5-7 leaves (pairwise Reduce_scatter at p = 5..7): the 8-leaf
+     * chain body with a run-time leaf count, else its masked program */
+    if (fixed && tree_mask == 0 && k >= 4 && chain_mask == mvx_chain_mask(k) && (k == 4 || cfg.chain_rt || k == 8))
+        return k == 4 ? ks->chain4 : ks->chain8;
+    if (cfg.prog_u == 2 && ks->prog2.var[V_CACHED].fn) return ks->prog2;
+    if (k <= 4 && cfg.prog4) return ks->prog4;
+    return ks->prog;
 }
 
-static int launch(const KSet *ks, const KFam &F, Params &P, hipStream_t stream)
+// The alignment rule, and nothing else -- the rule the work on mutually
+// misaligned operands will change.  The 16-byte path needs the destination,
+// every source and every fold partner on one residue m mod 16, and a whole
+// number of elements up to the next 16-byte boundary: then `head` scalar
+// elements lead to `nvec` whole chunks (the rest is the scalar tail);
+// otherwise every element goes the scalar way.  Reads P's addresses and n.
+struct Split { long head, nvec; int vec_ok; };
+static Split split(const Params &P, int esize, int chunk)
 {
-    init_env();
-    int nleaves = 0;
-    for (int q = 0; q < P.k; ++q) nleaves += 1 + (P.fold[q] != nullptr);
-    const int nt = (long)(nleaves + 1) * P.n * ks->esize >= g_nt_min_bytes;
-    const void *fn = F.fn[nt];
-    const int unroll = F.unroll[nt];
-    const size_t lds = nt ? g_cap_lds[F.fam] : 0;
-    const int es = ks->esize;
     const uintptr_t m = (uintptr_t)P.dst & 15;
     bool same = true;
     for (int q = 0; q < P.k; ++q) {
@@ -223,54 +234,109 @@ static int launch(const KSet *ks, const KFam &F, Params &P, hipStream_t stream)
         if (P.fold[q] && ((uintptr_t)P.fold[q] & 15) != m) same = false;
     }
     const long pre = (long)((16 - m) & 15);
-    if (same && pre % es == 0) {
-        long head = pre / es;
-        if (head > P.n) head = P.n;
-        P.head = head;
-        P.nvec = (P.n - head) * es / ks->chunk;
-        P.vec_ok = 1;
-    } else {
-        P.head = 0;
-        P.nvec = 0;
-        P.vec_ok = 0;
-    }
-    bool folded = false;
-    for (int q = 0; q < P.k; ++q) folded |= P.fold[q] != nullptr;
-    const bool body_k = P.k == F.body_k || (F.body_kmin && P.k >= F.body_kmin && P.k <= F.body_k);
-    if (nt && F.body && !g_no_body && body_k && P.vec_ok && P.head == 0 && P.nvec > 0 &&
-        P.nvec * ks->chunk == P.n * es && !folded) {
-        BodyParams B;
+    if (!same || pre % esize != 0) return {0, 0, 0};
+    const long head = pre / esize < P.n ? pre / esize : P.n;
+    return {head, (P.n - head) * esize / chunk, 1};
+}
+
+// What run() launches, and what mvx_op_plan / mvx_hip_last_* report.
+struct Plan {
+    const void *fn;
+    SymFn name;
+    char tag[96];          // "sum_f32_k2_nt"
+    unsigned blocks;
+    size_t lds;            // dynamic LDS bytes: the residency cap
+    bool body;             // the kernel takes BodyParams
+};
+
+// P with split()'s answer in it; nfold of its leaves are folded.
+static Plan plan(const KSet *ks, const KFam &F, const Params &P, int nfold, const Config &cfg)
+{
+    const int es = ks->esize;
+    const int nt = (long)(P.k + nfold + 1) * P.n * es >= cfg.nt_min_bytes;
+    const KVar &B = F.var[V_BODY];
+    const bool body = nt && B.fn && !cfg.no_body && P.k >= B.kmin && P.k <= B.kmax && P.vec_ok && P.head == 0 &&
+                      P.nvec > 0 && P.nvec * ks->chunk == P.n * es && !nfold;
+    const KVar &V = body ? B : F.var[nt];
+    const long per_block = (long)V.unroll * 256;
+    long work = body ? (P.nvec * V.units + per_block - 1) / per_block
+                     : P.vec_ok ? (P.nvec + per_block - 1) / per_block : (P.n + 255) / 256;
+    if (work < 1) work = 1;
+    const long fam_cap[FAM_N] = {cfg.cap_apply, cfg.cap_prog, cfg.cap_tree};
+    Plan pl;
+    pl.fn = V.fn;
+    pl.name = V.name;
+    snprintf(pl.tag, sizeof pl.tag, "%s_k%d%s", ks->name, P.k, nt ? "_nt" : "");
+    pl.blocks = (unsigned)(work < cfg.block_cap ? work : cfg.block_cap);
+    pl.lds = body ? cap_lds(V.cap) : nt ? cap_lds((int)fam_cap[F.fam]) : 0;
+    pl.body = body;
+    return pl;
+}
+
+// choose_family, split and plan for the leaves and program in P
+static Plan plan_params(const KSet *ks, Params &P)
+{
+    const Config &cfg = config();
+    int nfold = 0;
+    for (int q = 0; q < P.k; ++q) nfold += P.fold[q] != nullptr;
+    const KFam &F = choose_family(ks, cfg, P.k, P.tree_mask, P.chain_mask, nfold > 0);
+    const Split s = split(P, ks->esize, ks->chunk);
+    P.head = s.head;
+    P.nvec = s.nvec;
+    P.vec_ok = s.vec_ok;
+    return plan(ks, F, P, nfold, cfg);
+}
+
+static Plan g_last;        // the last launch (not thread-safe)
+
+static int run(const Plan &pl, const Params &P, hipStream_t stream)
+{
+    BodyParams B;
+    void *args[] = {const_cast<Params *>(&P)};
+    if (pl.body) {
         memset(&B, 0, sizeof B);
         for (int q = 0; q < P.k; ++q) B.src[q] = reinterpret_cast<const u32x4 *>(P.src[q]);
         B.dst = reinterpret_cast<u32x4 *>(P.dst);
         B.nvec = P.nvec;
         B.k = P.k;
-        long work = (P.nvec * F.body_units + F.body_unroll * 256 - 1) / (F.body_unroll * 256);
-        const unsigned blocks = (unsigned)(work < g_block_cap ? work : g_block_cap);
-        void *bargs[] = {&B};
-        const size_t blds = cap_lds(F.body_cap);
-        hipError_t e = hipLaunchKernel(F.body, dim3(blocks), dim3(256), bargs, blds, stream);
-        g_last_blocks = blocks;
-        g_last_lds = blds;
-        g_last_fn = F.body;
-        snprintf(g_last_buf, sizeof g_last_buf, "%s_k%d_nt", ks->name, P.k);
-        g_last = g_last_buf;
-        g_last_sym = F.body_sym();
-        return e == hipSuccess ? MPI_SUCCESS : MPI_ERR_OTHER;
+        args[0] = &B;
     }
-    long work = P.vec_ok ? (P.nvec + unroll * 256 - 1) / (unroll * 256)
-                         : (P.n + 255) / 256;
-    if (work < 1) work = 1;
-    const unsigned blocks = (unsigned)(work < g_block_cap ? work : g_block_cap);
-    void *args[] = {&P};
-    hipError_t e = hipLaunchKernel(fn, dim3(blocks), dim3(256), args, lds, stream);
-    g_last_blocks = blocks;
-    g_last_lds = lds;
-    g_last_fn = fn;
-    snprintf(g_last_buf, sizeof g_last_buf, "%s_k%d%s", ks->name, P.k, nt ? "_nt" : "");
-    g_last = g_last_buf;
-    g_last_sym = F.sym[nt]();
+    hipError_t e = hipLaunchKernel(pl.fn, dim3(pl.blocks), dim3(256), args, pl.lds, stream);
+    g_last = pl;
     return e == hipSuccess ? MPI_SUCCESS : MPI_ERR_OTHER;
+}
+
+// The argument checks of mvx_op_program, then P: MPI_SUCCESS (*ksp null for
+// n == 0: nothing to do) or the error code
+static int program_params(int op, int dtype, const void *const *srcs, const void *const *fold, int k,
+                          unsigned tree_mask, unsigned chain_mask, const void *dst, size_t n,
+                          const KSet **ksp, Params &P)
+{
+    int rc;
+    const KSet *ks = lookup(op, dtype, &rc);
+    *ksp = nullptr;
+    if (!ks) return rc;
+    if (k < 1 || k > MVX_COMBINE_KMAX || !srcs) return MPI_ERR_ARG;
+    /* every step must stay inside the k leaves */
+    for (int l = 0; l < 3; ++l)
+        for (int q = 0; q < 8; ++q)
+            if ((tree_mask >> (l * 8 + q) & 1u) && q + (1 << l) >= k) return MPI_ERR_ARG;
+    if ((tree_mask >> 24) || (chain_mask & 1u) || (chain_mask >> k)) return MPI_ERR_ARG;
+    if (n == 0) return MPI_SUCCESS;
+    memset(&P, 0, sizeof P);
+    for (int q = 0; q < k; ++q) {
+        P.src[q] = (const char *)srcs[q];
+        P.fold[q] = fold ? (const char *)fold[q] : nullptr;
+    }
+    P.dst = (char *)dst;
+    P.n = (long)n;
+    P.k = k;
+    P.tree_mask = tree_mask;
+    P.chain_mask = chain_mask;
+    /* the only programs over <= 2 leaves: nothing, or y0 op y1 */
+    if (k == 2 && !(tree_mask & 1u) && !(chain_mask & 2u)) return MPI_ERR_ARG;
+    *ksp = ks;
+    return MPI_SUCCESS;
 }
 
 }  // namespace mvx
@@ -305,54 +371,38 @@ extern "C" int mvx_op_apply(int op, int dtype, const void *in, void *inout,
     P.dst = (char *)inout;
     P.n = (long)n;
     P.k = 2;
-    return launch(ks, ks->apply, P, (hipStream_t)stream);
+    return run(plan_params(ks, P), P, (hipStream_t)stream);
 }
 
 extern "C" int mvx_op_program(int op, int dtype, const void *const *srcs,
                               const void *const *fold, int k, unsigned tree_mask,
                               unsigned chain_mask, void *dst, size_t n, void *stream)
 {
-    int rc;
-    const KSet *ks = lookup(op, dtype, &rc);
-    if (!ks) return rc;
-    if (k < 1 || k > MVX_COMBINE_KMAX || !srcs) return MPI_ERR_ARG;
-    /* every step must stay inside the k leaves */
-    for (int l = 0; l < 3; ++l)
-        for (int q = 0; q < 8; ++q)
-            if ((tree_mask >> (l * 8 + q) & 1u) && q + (1 << l) >= k) return MPI_ERR_ARG;
-    if ((tree_mask >> 24) || (chain_mask & 1u) || (chain_mask >> k)) return MPI_ERR_ARG;
-    if (n == 0) return MPI_SUCCESS;
+    const KSet *ks;
     Params P;
-    memset(&P, 0, sizeof P);
-    for (int q = 0; q < k; ++q) {
-        P.src[q] = (const char *)srcs[q];
-        P.fold[q] = fold ? (const char *)fold[q] : nullptr;
-    }
-    P.dst = (char *)dst;
-    P.n = (long)n;
-    P.k = k;
-    P.tree_mask = tree_mask;
-    P.chain_mask = chain_mask;
-    if (k <= 2) {
-        /* the only programs over <= 2 leaves: nothing, or y0 op y1 */
-        if (k == 2 && !(tree_mask & 1u) && !(chain_mask & 2u)) return MPI_ERR_ARG;
-        return launch(ks, ks->apply, P, (hipStream_t)stream);
-    }
-    init_env();
-    bool folded = false;
-    for (int q = 0; q < k; ++q) folded |= P.fold[q] != nullptr;
-    if (!g_generic_only && !folded && chain_mask == 0 && (k == 8 || k == 4) && tree_mask == mvx_tree_mask(k))
-        return launch(ks, k == 8 ? ks->tree8 : ks->tree4, P, (hipStream_t)stream);
-    /* chains of 5-7 leaves (pairwise Reduce_scatter at p = 5..7): the 8-leaf
-     * chain body with a run-time leaf count, else its masked program */
-    if (!g_generic_only && !folded && tree_mask == 0 && k >= 4 && chain_mask == mvx_chain_mask(k) &&
-        (k == 4 || g_chain_rt || k == 8))
-        return launch(ks, k == 4 ? ks->chain4 : ks->chain8, P, (hipStream_t)stream);
-    if (g_prog_u == 2 && ks->prog2.fn[0])
-        return launch(ks, ks->prog2, P, (hipStream_t)stream);
-    if (k <= 4 && g_prog4)
-        return launch(ks, ks->prog4, P, (hipStream_t)stream);
-    return launch(ks, ks->prog, P, (hipStream_t)stream);
+    const int rc = program_params(op, dtype, srcs, fold, k, tree_mask, chain_mask, dst, n, &ks, P);
+    if (rc != MPI_SUCCESS || !ks) return rc;
+    return run(plan_params(ks, P), P, (hipStream_t)stream);
+}
+
+extern "C" int mvx_op_plan(int op, int dtype, const void *const *srcs, const void *const *fold, int k,
+                           unsigned tree_mask, unsigned chain_mask, const void *dst, size_t n,
+                           struct mvx_launch_plan *out)
+{
+    const KSet *ks;
+    Params P;
+    const int rc = program_params(op, dtype, srcs, fold, k, tree_mask, chain_mask, dst, n, &ks, P);
+    if (rc != MPI_SUCCESS) return rc;
+    if (!out) return MPI_ERR_ARG;
+    memset(out, 0, sizeof *out);
+    out->symbol = "";
+    if (!ks) return MPI_SUCCESS;
+    const Plan pl = plan_params(ks, P);
+    out->symbol = pl.name();
+    memcpy(out->tag, pl.tag, sizeof out->tag);
+    out->blocks = pl.blocks;
+    out->dynamic_lds = pl.lds;
+    return MPI_SUCCESS;
 }
 
 extern "C" unsigned mvx_tree_mask(int k)
@@ -383,24 +433,24 @@ extern "C" int mvx_op_combine(int op, int dtype, const void *const *srcs,
 
 extern "C" void mvx_hip_set_launch(int block_cap, int nt_min_bytes_log2)
 {
-    init_env();
-    if (block_cap > 0) g_block_cap = block_cap;
-    if (nt_min_bytes_log2 > 0) g_nt_min_bytes = 1L << nt_min_bytes_log2;
-    if (nt_min_bytes_log2 < 0) g_nt_min_bytes = 1L << 62;   // never non-temporal
+    config();
+    if (block_cap > 0) g_cfg.block_cap = block_cap;
+    if (nt_min_bytes_log2 > 0) g_cfg.nt_min_bytes = 1L << nt_min_bytes_log2;
+    if (nt_min_bytes_log2 < 0) g_cfg.nt_min_bytes = 1L << 62;   // never non-temporal
 }
 
-extern "C" const char *mvx_hip_last_kernel(void) { return g_last; }
+extern "C" const char *mvx_hip_last_kernel(void) { return g_last.tag; }
 
-extern "C" const char *mvx_hip_last_kernel_symbol(void) { return g_last_sym; }
+extern "C" const char *mvx_hip_last_kernel_symbol(void) { return g_last.name ? g_last.name() : ""; }
 
 extern "C" void mvx_hip_last_launch(unsigned *blocks, size_t *dynamic_lds, int *blocks_per_cu)
 {
-    if (blocks) *blocks = g_last_blocks;
-    if (dynamic_lds) *dynamic_lds = g_last_lds;
+    if (blocks) *blocks = g_last.blocks;
+    if (dynamic_lds) *dynamic_lds = g_last.lds;
     if (blocks_per_cu) {
         int occ = 0;
-        if (!g_last_fn ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, g_last_fn, 256, g_last_lds) != hipSuccess) {
+        if (!g_last.fn ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, g_last.fn, 256, g_last.lds) != hipSuccess) {
             (void)hipGetLastError();
             occ = 0;
         }

@@ -1,0 +1,404 @@
+#pragma once
+// mvx_ops_fn.h -- the ops of the MPI local reduction path on elements and on
+// chunks (what one lane moves per operand per step): element layouts, F<op, T>,
+// Chunk / CG, the chunk op CF with its SWAR and packed-16 forms.  Device code
+// only; the kernels that use them are in mvx_ops_kern.h (design notes there).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mvx_xf80.h"
+
+namespace mvx {
+
+enum { OMAX = 0, OMIN, OSUM, OPROD, OLAND, OBAND, OLOR, OBOR, OLXOR, OBXOR,
+       OMINLOC, OMAXLOC };
+
+// Element layouts: the reference's C types on x86-64 LP64.
+struct cf32 { float re, im; };                          // global_ops.c:43-46
+struct cf64 { double re, im; };                         // global_ops.c:48-51
+struct pfi { float v; int32_t l; };                     // initdte.c:74-78
+// The padding is an explicit member so the inout operand's padding bytes are
+// carried through the register copy and written back unchanged (an unnamed
+// hole is `undef` to LLVM); the reference never writes them either
+// (global_ops.c:1335-1346 assign value and loc only).
+struct pdi { double v; int32_t l; int32_t pad; };       // 16 B
+struct pli { int64_t v; int32_t l; int32_t pad; };      // 16 B
+struct psi { int16_t v; int16_t pad; int32_t l; };      // 8 B
+struct pii { int32_t v; int32_t l; };                   // MPI_2INT
+static_assert(sizeof(pdi) == 16 && sizeof(pli) == 16 && sizeof(psi) == 8, "");
+// contiguous count-2 types over one base type (MPI_2INT's family, e.g.
+// MPI_Type_contiguous(2, MPI_FLOAT)): value and loc both of the base type,
+// global_ops.c:1387-1503 / 1625-1740
+template <typename B> struct pp { B v; B l; };
+static_assert(sizeof(pp<int8_t>) == 2 && sizeof(pp<double>) == 16, "");
+
+// x87 long double (16-byte slot) and MPI_LONG_DOUBLE_INT (32 bytes):
+// integer emulation of the x87 unit, mvx_xf80.h
+using xf::xf80;
+using xf::pxi;
+static_assert(sizeof(xf80) == 16 && sizeof(pxi) == 32, "");
+template <typename B> struct pp;
+
+// the x87 types: every op is dozens of integer instructions, so their
+// combines are ALU-bound and keep full occupancy (no k_tree_body, no
+// residency cap: the 8-leaf x87 SUM tree ran 109.7 us at 2 blocks per CU
+// against 74.4 us uncapped, profiles/r02/bench_kernels_x87.jsonl).  The
+// MPI_LONG_DOUBLE_INT MAXLOC / MINLOC trees have their own body kernel,
+// k_pxi_loc_body (one element per lane pair).
+template <typename T> struct alu_heavy { static constexpr bool v = false; };
+template <> struct alu_heavy<xf80> { static constexpr bool v = true; };
+template <> struct alu_heavy<pxi> { static constexpr bool v = true; };
+template <> struct alu_heavy<pp<xf80>> { static constexpr bool v = true; };
+
+// ---------------------------------------------------------------------------
+// the ops: F<op, T>::f(a, b) returns the new inout value (a = inout, b = in)
+
+template <int O, typename T> struct F;
+
+template <typename T> struct F<OMAX, T> {     // coll.h:17-18
+    static __device__ __forceinline__ T f(T a, T b) { return (b > a) ? b : a; }
+};
+template <typename T> struct F<OMIN, T> {     // coll.h:14-15
+    static __device__ __forceinline__ T f(T a, T b) { return (a > b) ? b : a; }
+};
+
+template <typename T> __device__ __forceinline__ T add_(T a, T b) { return (T)(a + b); }
+template <typename T> __device__ __forceinline__ T mul_(T a, T b) { return (T)(a * b); }
+// promote narrow unsigned before multiplying so the product cannot overflow int
+template <> __device__ __forceinline__ uint8_t mul_(uint8_t a, uint8_t b)
+{ return (uint8_t)((uint32_t)a * (uint32_t)b); }
+template <> __device__ __forceinline__ uint16_t mul_(uint16_t a, uint16_t b)
+{ return (uint16_t)((uint32_t)a * (uint32_t)b); }
+
+template <typename T> struct F<OSUM, T> {
+    static __device__ __forceinline__ T f(T a, T b) { return add_(a, b); }
+};
+template <> struct F<OSUM, cf32> {
+    static __device__ __forceinline__ cf32 f(cf32 a, cf32 b)
+    { cf32 r; r.re = a.re + b.re; r.im = a.im + b.im; return r; }
+};
+template <> struct F<OSUM, cf64> {
+    static __device__ __forceinline__ cf64 f(cf64 a, cf64 b)
+    { cf64 r; r.re = a.re + b.re; r.im = a.im + b.im; return r; }
+};
+template <typename T> struct F<OPROD, T> {
+    static __device__ __forceinline__ T f(T a, T b) { return mul_(a, b); }
+};
+template <> struct F<OPROD, cf32> {            // global_ops.c:513-521
+    static __device__ __forceinline__ cf32 f(cf32 c, cf32 b)
+    { cf32 r; r.re = c.re * b.re - c.im * b.im; r.im = c.im * b.re + c.re * b.im; return r; }
+};
+template <> struct F<OPROD, cf64> {            // global_ops.c:523-531
+    static __device__ __forceinline__ cf64 f(cf64 c, cf64 b)
+    { cf64 r; r.re = c.re * b.re - c.im * b.im; r.im = c.im * b.re + c.re * b.im; return r; }
+};
+template <typename T> struct F<OLAND, T> {
+    static __device__ __forceinline__ T f(T a, T b) { return (a != T(0) && b != T(0)) ? T(1) : T(0); }
+};
+template <typename T> struct F<OLOR, T> {
+    static __device__ __forceinline__ T f(T a, T b) { return (a != T(0) || b != T(0)) ? T(1) : T(0); }
+};
+template <typename T> struct F<OLXOR, T> {
+    static __device__ __forceinline__ T f(T a, T b) { return ((a != T(0)) != (b != T(0))) ? T(1) : T(0); }
+};
+template <typename T> struct F<OBAND, T> {
+    static __device__ __forceinline__ T f(T a, T b) { return (T)(a & b); }
+};
+template <typename T> struct F<OBOR, T> {
+    static __device__ __forceinline__ T f(T a, T b) { return (T)(a | b); }
+};
+template <typename T> struct F<OBXOR, T> {
+    static __device__ __forceinline__ T f(T a, T b) { return (T)(a ^ b); }
+};
+// MAXLOC / MINLOC: global_ops.c:1297-1309 and 1524-1536, as selects
+// (no divergent branches): equal values keep a's value and the smaller loc;
+// otherwise b wins only if strictly larger (smaller); a NaN on either side
+// compares false both ways, so a is kept.  The padding member comes from a.
+template <typename T, bool MIN>
+__device__ __forceinline__ T loc_op(T a, T b)
+{
+    const bool eq = a.v == b.v;
+    const bool take = MIN ? (a.v > b.v) : (a.v < b.v);
+    const decltype(a.l) lmin = (a.l > b.l) ? b.l : a.l;   // MPIR_MIN, coll.h:14-15
+    T r = a;
+    r.v = take ? b.v : a.v;
+    r.l = eq ? lmin : (take ? b.l : a.l);
+    return r;
+}
+template <typename T> struct F<OMAXLOC, T> {
+    static __device__ __forceinline__ T f(T a, T b) { return loc_op<T, false>(a, b); }
+};
+template <typename T> struct F<OMINLOC, T> {
+    static __device__ __forceinline__ T f(T a, T b) { return loc_op<T, true>(a, b); }
+};
+
+// the x87 types (global_ops.c:149-155 and the HAVE_LONG_DOUBLE case of every
+// op; 1365-1378 / 1605-1618 for LONG_DOUBLE_INT)
+template <> struct F<OMAX, xf80> { static __device__ __forceinline__ xf80 f(xf80 a, xf80 b) { return xf::max(a, b); } };
+template <> struct F<OMIN, xf80> { static __device__ __forceinline__ xf80 f(xf80 a, xf80 b) { return xf::min(a, b); } };
+template <> struct F<OSUM, xf80> { static __device__ __forceinline__ xf80 f(xf80 a, xf80 b) { return xf::add(a, b); } };
+template <> struct F<OPROD, xf80> { static __device__ __forceinline__ xf80 f(xf80 a, xf80 b) { return xf::mul(a, b); } };
+template <> struct F<OLAND, xf80> { static __device__ __forceinline__ xf80 f(xf80 a, xf80 b) { return xf::land(a, b); } };
+template <> struct F<OLOR, xf80> { static __device__ __forceinline__ xf80 f(xf80 a, xf80 b) { return xf::lor(a, b); } };
+template <> struct F<OLXOR, xf80> { static __device__ __forceinline__ xf80 f(xf80 a, xf80 b) { return xf::lxor(a, b); } };
+template <> struct F<OMAXLOC, pxi> { static __device__ __forceinline__ pxi f(pxi a, pxi b) { return xf::loc<false>(a, b); } };
+template <> struct F<OMINLOC, pxi> { static __device__ __forceinline__ pxi f(pxi a, pxi b) { return xf::loc<true>(a, b); } };
+
+// contiguous(2, MPI_LONG_DOUBLE) pairs (global_ops.c:1483-1496, 1720-1733):
+// x87 compares of the values; equal -> loc = MPIR_MIN(a.l, b.l) (x87 select);
+// b strictly larger (smaller) -> both of b's 10-byte values.  Each slot's
+// padding stays the inout operand's.
+template <bool MIN>
+__device__ __forceinline__ pp<xf80> xloc2(pp<xf80> a, pp<xf80> b)
+{
+    const int c = xf::cmp(a.v, b.v);
+    pp<xf80> r = a;
+    if (c == 0) {
+        r.l = xf::min(a.l, b.l);
+    } else if (c == (MIN ? 1 : -1)) {
+        r.v = xf::with_bits(a.v, b.v.m, b.v.se);
+        r.l = xf::with_bits(a.l, b.l.m, b.l.se);
+    }
+    return r;
+}
+template <> struct F<OMAXLOC, pp<xf80>> { static __device__ __forceinline__ pp<xf80> f(pp<xf80> a, pp<xf80> b) { return xloc2<false>(a, b); } };
+template <> struct F<OMINLOC, pp<xf80>> { static __device__ __forceinline__ pp<xf80> f(pp<xf80> a, pp<xf80> b) { return xloc2<true>(a, b); } };
+
+// EXTENSION beyond the reference: the 16-bit floating types MVX_FLOAT16 and
+// MVX_BFLOAT16 (include/mvx_mpi.h), treated as global_ops.c would treat one
+// more C floating type next to float and double.  f16 is the compiler's IEEE
+// binary16 and takes the generic ops above: every step is one correctly
+// rounded half-precision instruction, subnormals kept.  bf16 is the upper
+// half of a binary32: widened exactly by a shift, combined in f32 and
+// narrowed round-to-nearest-even by the __bf16 conversion -- a sum or a
+// product of two bf16 values rounded to f32 and then to bf16 equals the
+// directly rounded one (24 >= 2 * 8 + 2; the product is exact in f32).  No
+// step's f32 value is carried into the next.  MAX / MIN compare the widened
+// values and keep the chosen operand's 16 bits; the logical ops store 1.0
+// (0x3F80) or 0.
+typedef _Float16 f16;
+struct bf16 { uint16_t u; };
+static_assert(sizeof(f16) == 2 && sizeof(bf16) == 2, "");
+
+__device__ __forceinline__ float bits_f32(uint32_t w)
+{
+    float f;
+    __builtin_memcpy(&f, &w, 4);
+    return f;
+}
+__device__ __forceinline__ bf16 bf_narrow(float f)
+{
+    const __bf16 h = (__bf16)f;
+    bf16 r;
+    __builtin_memcpy(&r.u, &h, 2);
+    return r;
+}
+template <int O>
+__device__ __forceinline__ bf16 bf_op(bf16 a, bf16 b)
+{
+    const float x = bits_f32((uint32_t)a.u << 16), y = bits_f32((uint32_t)b.u << 16);
+    bf16 t;
+    if constexpr (O == OMAX) return (y > x) ? b : a;
+    else if constexpr (O == OMIN) return (x > y) ? b : a;
+    else if constexpr (O == OSUM) return bf_narrow(x + y);
+    else if constexpr (O == OPROD) return bf_narrow(x * y);
+    else if constexpr (O == OLAND) { t.u = (x != 0.0f && y != 0.0f) ? 0x3f80 : 0; return t; }
+    else if constexpr (O == OLOR) { t.u = (x != 0.0f || y != 0.0f) ? 0x3f80 : 0; return t; }
+    else { static_assert(O == OLXOR, ""); t.u = ((x != 0.0f) != (y != 0.0f)) ? 0x3f80 : 0; return t; }
+}
+#define MVX_BF16_OP(O)                                                        \
+    template <> struct F<O, bf16> {                                           \
+        static __device__ __forceinline__ bf16 f(bf16 a, bf16 b) { return bf_op<O>(a, b); } \
+    };
+MVX_BF16_OP(OMAX) MVX_BF16_OP(OMIN) MVX_BF16_OP(OSUM) MVX_BF16_OP(OPROD)
+MVX_BF16_OP(OLAND) MVX_BF16_OP(OLOR) MVX_BF16_OP(OLXOR)
+#undef MVX_BF16_OP
+
+#ifdef MVX_OPS_LOGICAL_TU   // one TU owns the .TRUE. / .FALSE. words (mvx_ops_logic.hip)
+// MPI_LOGICAL (dte_type MPIR_LOGICAL, one MPI_Fint): LAND / LOR / LXOR
+// compare each word with the Fortran .TRUE. and store .TRUE. or .FALSE.
+// (global_ops.c:646-655, 875-884, 1104-1113 with mpi_fort.h:11-19:
+// FROM_FLOG(x) = x == MPIR_F_TRUE, TO_FLOG(v) = v ? MPIR_F_TRUE :
+// MPIR_F_FALSE).  BAND / BOR / BXOR are bitwise on the word (678-684 ...)
+// and run the 32-bit integer kernels.
+struct flog { int32_t v; };
+__constant__ int32_t g_flog[2] = {1, 0};     // MPIR_F_TRUE, MPIR_F_FALSE (gfortran)
+__device__ __forceinline__ flog to_flog(bool t) { flog r; r.v = t ? g_flog[0] : g_flog[1]; return r; }
+template <> struct F<OLAND, flog> {
+    static __device__ __forceinline__ flog f(flog a, flog b) { return to_flog(a.v == g_flog[0] && b.v == g_flog[0]); }
+};
+template <> struct F<OLOR, flog> {
+    static __device__ __forceinline__ flog f(flog a, flog b) { return to_flog(a.v == g_flog[0] || b.v == g_flog[0]); }
+};
+template <> struct F<OLXOR, flog> {
+    static __device__ __forceinline__ flog f(flog a, flog b) { return to_flog((a.v == g_flog[0]) != (b.v == g_flog[0])); }
+};
+#endif
+
+// A chunk is what one lane moves per operand per step: 16 bytes of
+// elements, or one element of a wider type (MPI_LONG_DOUBLE_INT, 32 bytes:
+// two dwordx4).  Moved to/from the registers by memcpy (a well-defined bit
+// copy that keeps pair padding bytes; union punning lets clang drop the
+// element writes).
+template <typename T> struct CG {
+    static constexpr int bytes = sizeof(T) > 16 ? (int)sizeof(T) : 16;
+    static constexpr int w = bytes / 16;          // dwordx4 per chunk
+    static constexpr int v = bytes / (int)sizeof(T);  // elements per chunk
+};
+
+template <typename T> struct Chunk {
+    T e[CG<T>::v];
+};
+// 1-byte elements stay in their four 32-bit words (the SWAR chunk op, CF8):
+// as 16 byte members the loads and stores were split into bytes and packed
+// again around every op
+template <> struct Chunk<uint8_t> { uint32_t w[4]; };
+template <> struct Chunk<int8_t> { uint32_t w[4]; };
+
+// The op over a whole chunk, a = op(a, b) element by element.  One-byte
+// types run as SWAR on the chunk's four 32-bit words: element by element
+// the compiler extracted, combined and re-packed every byte, and the 1-byte
+// apply kernels ran at 0.65-0.73 of HBM peak against 0.78-0.81 for every
+// wider type (tools/bench_kernels.py all, profiles/r05/bench_kernels_all.jsonl).
+template <int O, typename T>
+struct CF {
+    static __device__ __forceinline__ void f(Chunk<T> &a, const Chunk<T> &b)
+    {
+#pragma unroll
+        for (int j = 0; j < CG<T>::v; ++j) a.e[j] = F<O, T>::f(a.e[j], b.e[j]);
+    }
+};
+
+typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));   // one packed-16 register
+
+// per byte of a word: 0x80 if the byte is nonzero, else 0
+__device__ __forceinline__ uint32_t swar_nz(uint32_t x)
+{
+    return (((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u;
+}
+
+// bytes as two packed-16 lanes each (even bytes, odd bytes), op lane-wise,
+// low 8 bits of each lane kept: unsigned MAX / MIN, wrapping PROD
+template <int O>
+__device__ __forceinline__ uint32_t swar_p16(uint32_t a, uint32_t b)
+{
+    const uint32_t ae = a & 0x00ff00ffu, ao = (a >> 8) & 0x00ff00ffu;
+    const uint32_t be = b & 0x00ff00ffu, bo = (b >> 8) & 0x00ff00ffu;
+    u16x2 xe, xo, ye, yo, re, ro;
+    __builtin_memcpy(&xe, &ae, 4); __builtin_memcpy(&xo, &ao, 4);
+    __builtin_memcpy(&ye, &be, 4); __builtin_memcpy(&yo, &bo, 4);
+    if constexpr (O == OMAX) { re = __builtin_elementwise_max(xe, ye); ro = __builtin_elementwise_max(xo, yo); }
+    else if constexpr (O == OMIN) { re = __builtin_elementwise_min(xe, ye); ro = __builtin_elementwise_min(xo, yo); }
+    else { re = xe * ye; ro = xo * yo; }
+    uint32_t e, o;
+    __builtin_memcpy(&e, &re, 4); __builtin_memcpy(&o, &ro, 4);
+    return (e & 0x00ff00ffu) | ((o & 0x00ff00ffu) << 8);
+}
+
+// one word of four 1-byte elements, op O; SIGNED: int8_t MAX / MIN
+template <int O, bool SIGNED>
+__device__ __forceinline__ uint32_t swar8(uint32_t a, uint32_t b)
+{
+    if constexpr (O == OBAND) return a & b;
+    else if constexpr (O == OBOR) return a | b;
+    else if constexpr (O == OBXOR) return a ^ b;
+    else if constexpr (O == OSUM) return ((a & 0x7f7f7f7fu) + (b & 0x7f7f7f7fu)) ^ ((a ^ b) & 0x80808080u);
+    else if constexpr (O == OLAND) return (swar_nz(a) & swar_nz(b)) >> 7;
+    else if constexpr (O == OLOR) return (swar_nz(a) | swar_nz(b)) >> 7;
+    else if constexpr (O == OLXOR) return (swar_nz(a) ^ swar_nz(b)) >> 7;
+    else if constexpr (SIGNED) return swar_p16<O>(a ^ 0x80808080u, b ^ 0x80808080u) ^ 0x80808080u;   // biased order
+    else return swar_p16<O>(a, b);
+}
+
+template <int O, bool SIGNED>
+struct CF8 {
+    template <typename T>
+    static __device__ __forceinline__ void f(Chunk<T> &a, const Chunk<T> &b)
+    {
+#pragma unroll
+        for (int w = 0; w < 4; ++w) a.w[w] = swar8<O, SIGNED>(a.w[w], b.w[w]);
+    }
+};
+template <int O> struct CF<O, uint8_t> {
+    static __device__ __forceinline__ void f(Chunk<uint8_t> &a, const Chunk<uint8_t> &b) { CF8<O, false>::f(a, b); }
+};
+template <int O> struct CF<O, int8_t> {
+    static __device__ __forceinline__ void f(Chunk<int8_t> &a, const Chunk<int8_t> &b) { CF8<O, true>::f(a, b); }
+};
+
+// The 16-bit floating types stay in their four 32-bit words too, two elements
+// a word: W16<O, T>::f is the op on one word.
+template <> struct Chunk<f16> { uint32_t w[4]; };
+template <> struct Chunk<bf16> { uint32_t w[4]; };
+
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+template <int O, typename T> struct W16;
+
+// f16: SUM / PROD are one packed instruction (v_pk_add_f16 / v_pk_mul_f16);
+// MAX / MIN are a compare and a select per half, not v_pk_max / v_pk_min,
+// whose NaN and signed-zero results are not the select's.
+template <int O> struct W16<O, f16> {
+    static __device__ __forceinline__ uint32_t f(uint32_t a, uint32_t b)
+    {
+        f16x2 x, y, r;
+        __builtin_memcpy(&x, &a, 4);
+        __builtin_memcpy(&y, &b, 4);
+        if constexpr (O == OSUM) r = x + y;
+        else if constexpr (O == OPROD) r = x * y;
+        else { r.x = F<O, f16>::f(x.x, y.x); r.y = F<O, f16>::f(x.y, y.y); }
+        uint32_t w;
+        __builtin_memcpy(&w, &r, 4);
+        return w;
+    }
+};
+
+// bf16: the low half widens by a shift, the high half by a mask; SUM / PROD
+// narrow both f32 results with one packed conversion (v_cvt_pk_bf16_f32);
+// MAX / MIN select the original halves.
+template <int O> struct W16<O, bf16> {
+    static __device__ __forceinline__ uint32_t f(uint32_t a, uint32_t b)
+    {
+        const float xl = bits_f32(a << 16), xh = bits_f32(a & 0xffff0000u);
+        const float yl = bits_f32(b << 16), yh = bits_f32(b & 0xffff0000u);
+        if constexpr (O == OMAX || O == OMIN) {
+            const bool tl = O == OMAX ? (yl > xl) : (xl > yl);
+            const bool th = O == OMAX ? (yh > xh) : (xh > yh);
+            return ((tl ? b : a) & 0xffffu) | ((th ? b : a) & 0xffff0000u);
+        } else if constexpr (O == OSUM || O == OPROD) {
+            f32x2 r;
+            r.x = O == OSUM ? xl + yl : xl * yl;
+            r.y = O == OSUM ? xh + yh : xh * yh;
+            const bf16x2 h = __builtin_convertvector(r, bf16x2);
+            uint32_t w;
+            __builtin_memcpy(&w, &h, 4);
+            return w;
+        } else {
+            const bool al = xl != 0.0f, ah = xh != 0.0f, bl = yl != 0.0f, bh = yh != 0.0f;
+            bool tl, th;
+            if constexpr (O == OLAND) { tl = al && bl; th = ah && bh; }
+            else if constexpr (O == OLOR) { tl = al || bl; th = ah || bh; }
+            else { static_assert(O == OLXOR, ""); tl = al != bl; th = ah != bh; }
+            return (tl ? 0x3f80u : 0u) | (th ? 0x3f800000u : 0u);
+        }
+    }
+};
+
+template <int O, typename T>
+struct CF16 {
+    static __device__ __forceinline__ void f(Chunk<T> &a, const Chunk<T> &b)
+    {
+#pragma unroll
+        for (int w = 0; w < 4; ++w) a.w[w] = W16<O, T>::f(a.w[w], b.w[w]);
+    }
+};
+template <int O> struct CF<O, f16> {
+    static __device__ __forceinline__ void f(Chunk<f16> &a, const Chunk<f16> &b) { CF16<O, f16>::f(a, b); }
+};
+template <int O> struct CF<O, bf16> {
+    static __device__ __forceinline__ void f(Chunk<bf16> &a, const Chunk<bf16> &b) { CF16<O, bf16>::f(a, b); }
+};
+
+}  // namespace mvx

@@ -2,8 +2,8 @@
 // and MVX_BFLOAT16 (an extension beyond the reference, include/mvx_mpi.h):
 // the seven ops MPI_FLOAT has.  One translation unit of libmvx_hip.so of its
 // own -- 14 kernel sets, fewer than any of the other tables hold -- so the
-// kernel instantiations compile in parallel (mvx_ops_kern.h).
-#include "mvx_ops_kern.h"
+// kernel instantiations compile in parallel (mvx_ops_tab.h).
+#include "mvx_ops_tab.h"
 
 namespace mvx {
 

@@ -1,6 +1,6 @@
 // mvx_ops_loc.hip -- kernel table of MAXLOC, MINLOC (one translation unit of libmvx_hip.so,
-// so the kernel instantiations compile in parallel; mvx_ops_kern.h)
-#include "mvx_ops_kern.h"
+// so the kernel instantiations compile in parallel; mvx_ops_tab.h)
+#include "mvx_ops_tab.h"
 
 namespace mvx {
 

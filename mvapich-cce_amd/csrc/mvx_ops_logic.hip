@@ -1,8 +1,8 @@
 // mvx_ops_logic.hip -- kernel table of LAND, LOR, LXOR, BAND, BOR, BXOR
 // (one translation unit of libmvx_hip.so,
-// so the kernel instantiations compile in parallel; mvx_ops_kern.h)
+// so the kernel instantiations compile in parallel; mvx_ops_tab.h)
 #define MVX_OPS_LOGICAL_TU 1
-#include "mvx_ops_kern.h"
+#include "mvx_ops_tab.h"
 
 namespace mvx {
 

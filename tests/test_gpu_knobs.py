@@ -1,7 +1,8 @@
 """GPU: every kernel-selecting environment knob, each group in a fresh process.
 
-mvx_ops.hip, mvx_ops_kern.h and mvx_pack.hip read their knobs once into
-statics, so a knob can only be tested in a process that starts with it set.
+mvx_ops.hip (config(), into the Config of mvx_ops_tab.h) and mvx_pack.hip read
+their knobs once, so a knob can only be tested in a process that starts with
+it set.
 tests/knob_worker.py holds the groups (its ENV) and the checks; here one
 worker runs at a time, each under its own time limit, with the parent's
 environment plus the group's knobs.  A worker that ends by a signal, an

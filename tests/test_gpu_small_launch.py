@@ -16,15 +16,10 @@ import pytest
 
 import mvxtest as T
 import small_launch as SL
-from small_launch import SHAPE_CHAIN, SHAPE_TREE
+from small_launch import (BODY_NVEC, BODY_PAIRS, COMBINE_FAMILIES, COMBINE_NVEC, MISALIGNED_N, PXI_NVEC, SHAPE_CHAIN,
+                          SHAPE_TREE)
 
 pytestmark = pytest.mark.gpu
-
-BODY_NVEC = (1, 255, 256, 257, 511, 512, 513, 1025, 3372)
-BODY_PAIRS = [(102, 10), (111, 17), (105, 8), (110, 18), (103, 24), (100, 1), (103, 2), (108, 1)]
-PXI_NVEC = (1, 127, 128, 129, 255, 257, 1000)
-COMBINE_NVEC = (0, 1, 1023, 1024, 1025, 4099)
-MISALIGNED_N = (1, 255, 1000)
 
 
 @pytest.fixture
@@ -82,20 +77,6 @@ def test_long_double_int_pair_body_ragged(mvx, oracle, launch, op, cap):
         _capped(blocks, cap)
         if cap is None:
             assert blocks == (2 * n + 255) // 256
-
-
-# k_combine families on MPI_FLOAT SUM: (name, k, shape, folded, KMAX, U of the
-# cached build, U of the non-temporal build, PROG)
-COMBINE_FAMILIES = [
-    ("apply", 2, SHAPE_TREE, False, 2, 4, 4, 0),
-    ("masked-tree6", 6, SHAPE_TREE, False, 8, 1, 1, 0),
-    ("masked-chain7", 7, SHAPE_CHAIN, False, 8, 1, 1, 0),
-    ("masked-folded-tree8", 8, SHAPE_TREE, True, 8, 1, 1, 0),
-    ("prog4-k3", 3, SHAPE_TREE, False, 4, 2, 2, 0),
-    ("prog4-folded-k4", 4, SHAPE_CHAIN, True, 4, 2, 2, 0),
-    ("tree4-fallback", 4, SHAPE_TREE, False, 4, 1, 2, 1),
-    ("tree8-fallback", 8, SHAPE_TREE, False, 8, 1, 2, 1),
-]
 
 
 @pytest.mark.parametrize("nt", [1, 0])
