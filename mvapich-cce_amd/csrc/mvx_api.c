@@ -5,7 +5,7 @@
  *   MPI_Reduce_scatter (red_scat.c:60-90) -> intra_Reduce_scatter
  *   MPI_Scan      (scan.c:55-95)      -> MPIR_intra_Scan
  * Argument checks keep the reference's order and codes; one call becomes
- * this rank's plan (mvx_plan.c) run as a job (mvx_exec.c / mvx_stage.c).
+ * this rank's plan (mvx_plan.c) run as a job (mvx_graph.c / mvx_exec.c / mvx_stage.c).
  */
 #include <string.h>
 

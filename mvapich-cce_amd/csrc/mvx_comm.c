@@ -136,7 +136,7 @@ static int claim_shmem_block(void)
 
 /* MVX_EXCHANGE = p2p | pipe[:slices] | coll (default p2p);
  * MVX_HOST_PIPELINE = 1: host buffers at p > 1 take the sliced pipeline;
- * MVX_GRAPH = 1: device calls are captured and replayed as HIP graphs */
+ * the graph knobs are mvx_graph.c's */
 static void exchange_from_env(mvx_comm_t *c)
 {
     const char *e = getenv("MVX_EXCHANGE");
@@ -144,11 +144,7 @@ static void exchange_from_env(mvx_comm_t *c)
     c->exch = MVX_EXCH_P2P;
     c->exch_slices = 4;
     c->host_sliced = env_int("MVX_HOST_PIPELINE", &v) && v == 1;
-    c->graphs = env_int("MVX_GRAPH", &v) && v == 1;
-    c->graph_cap = GRAPH_CACHE;
-    if (env_int("MVX_GRAPH_CACHE", &v) && v >= 1 && v <= GRAPH_CACHE) c->graph_cap = v;
-    c->graph_evict = mvxi_graph_evict_default();
-    if (env_int("MVX_GRAPH_EVICT", &v) && v >= MVX_GRAPH_EVICT_NONE && v <= MVX_GRAPH_EVICT_ALL) c->graph_evict = v;
+    mvxi_graph_knobs(c);
     if (!e) return;
     if (!strncmp(e, "pipe", 4)) {
         c->exch = MVX_EXCH_PIPE;
@@ -156,22 +152,6 @@ static void exchange_from_env(mvx_comm_t *c)
     } else if (!strcmp(e, "coll")) {
         c->exch = MVX_EXCH_COLL;
     }
-}
-
-/* Which captured graphs may be destroyed mid-life on this HIP runtime.
- * HIP 7.0 (70051831, the runtime torch 2.10+rocm7.0 bundles) crashes in
- * hipGraphLaunch once execs of graphs with parallel branches (a fork / join
- * across streams) have been destroyed -- with no RCCL and no libmvx in the
- * process, while the same graphs kept alive, and single-branch graphs
- * destroyed, run clean (tools/graph_probe2.c churn_*);
- * HIP 7.2 (70226015, the image's /opt/rocm) runs all of it clean.  So from
- * 7.2 any graph may be destroyed; before it, only single-branch ones.
- * MVX_GRAPH_EVICT = 0 | 1 | 2 overrides (none / single-branch / all). */
-int mvxi_graph_evict_default(void)
-{
-    int v = 0;
-    if (hipRuntimeGetVersion(&v) != hipSuccess) { (void)hipGetLastError(); return MVX_GRAPH_EVICT_SERIAL; }
-    return v >= 70200000 ? MVX_GRAPH_EVICT_ALL : MVX_GRAPH_EVICT_SERIAL;
 }
 
 /* a new communicator's flavour: MVX_DEVICE names the reference device */
@@ -553,26 +533,6 @@ int mvx_comm_set_call_kinds(MPI_Comm comm, int kinds)
     return MPI_SUCCESS;
 }
 
-int mvx_comm_set_graphs(MPI_Comm comm, int on)
-{
-    mvx_comm_t *c = mvxi_get_comm(comm);
-    if (!c) return ERR_COMM_NULL_CODE;
-    /* turning graphs off keeps what was captured (destroyed with the
-     * communicator, mvx_exec.c); on again, they replay */
-    c->graphs = on ? 1 : 0;
-    c->graph_error = 0;
-    return MPI_SUCCESS;
-}
-
-int mvx_comm_last_graph(MPI_Comm comm, int *state, int *error)
-{
-    mvx_comm_t *c = mvxi_get_comm(comm);
-    if (!c) return ERR_COMM_NULL_CODE;
-    if (state) *state = c->last_graph;
-    if (error) *error = c->graph_error;
-    return MPI_SUCCESS;
-}
-
 int mvx_comm_last_exchange(MPI_Comm comm, int *mode)
 {
     mvx_comm_t *c = mvxi_get_comm(comm);
@@ -681,8 +641,6 @@ int mvx_comm_set_stream(MPI_Comm comm, void *stream)
 }
 
 /* ---- staging pools --------------------------------------------------------- */
-
-__thread int mvxi_capturing;
 
 int mvxi_grow(char **buf, size_t *have, size_t need)
 {

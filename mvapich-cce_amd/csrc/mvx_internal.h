@@ -14,8 +14,10 @@
  *   mvx_xport.c    transports: RCCL, caller-supplied, loopback (virtual)
  *   mvx_exec.c     one rank's plan on device buffers: phases A-C and the
  *                  exchange variants P2P / PIPE / COLL
- *   mvx_stage.c    host buffers (sliced pipeline, HBM mirrors) and packed
- *                  datatypes
+ *   mvx_graph.c    HIP graphs of device calls: the cache and its key,
+ *                  capture, replay, destruction, the graph knobs
+ *   mvx_stage.c    host buffers (operand kinds and registration holds,
+ *                  sliced pipeline, HBM mirrors) and packed datatypes
  *   mvx_api.c      the MPI entry points: argument checks, one call's job
  *   mvx_hostop.c   MPIR_SUM ... as MPI_User_functions on any memory
  *   mvx_host.c     buffer kinds, the host copy pool, the registration cache
@@ -152,12 +154,14 @@ typedef struct {
     unsigned long shold[MVX_MAXP], rhold[MVX_MAXP];   /* registration holds (mvxi_buf_kind_hold) */
 } job_t;
 
-MVXI int mvxi_job_kinds(job_t *J);
-/* the job is over (rc: its result; on failure the device is drained first,
- * as copies of a failed pipeline may still be in flight): drop its holds */
-MVXI void mvxi_job_release(job_t *J, int rc);
-MVXI void mvxi_graphs_clear(mvx_comm_t *c);
-MVXI int mvxi_run_device(mvx_comm_t *c, const job_t *J, hipStream_t st);
+/* the job issued on `st` (mvxi_run_device may capture or replay it instead) */
+MVXI int mvxi_run_device_eager(mvx_comm_t *c, const job_t *J, hipStream_t st);
+MVXI int mvxi_grow_pool(mvx_comm_t *c, size_t need);
+/* the communicator's non-blocking stream (created at first use): work of a
+ * null-stream call forked onto it and joined back */
+MVXI int mvxi_graph_streams(mvx_comm_t *c);
+MVXI int mvxi_null_fork(mvx_comm_t *c);
+MVXI int mvxi_null_join(mvx_comm_t *c);
 MVXI int mvxi_exec_group(rank_exec_t *X, mvx_xport *t, int nr, hipStream_t st, mvx_comm_t *timed);
 MVXI size_t mvxi_region_layout(mvx_comm_t *c, rank_exec_t *X, const job_t *J, const mvx_plan *Q, size_t *off);
 MVXI int mvxi_job_layout(mvx_comm_t *c, rank_exec_t *X, const job_t *J, const mvx_plan *Q);
@@ -185,6 +189,10 @@ typedef struct {                  /* a communicator's host-staging resources */
     hipEvent_t ein[STAGE_NB], eout[STAGE_NB], ex[STAGE_NB];
 } stage_res_t;
 
+MVXI int mvxi_job_kinds(job_t *J);
+/* the job is over (rc: its result; on failure the device is drained first,
+ * as copies of a failed pipeline may still be in flight): drop its holds */
+MVXI void mvxi_job_release(job_t *J, int rc);
 MVXI int mvxi_run_job(mvx_comm_t *c, job_t *J, hipStream_t st, int blocking);
 MVXI int mvxi_run_job_packed(mvx_comm_t *c, job_t *J, hipStream_t st, int blocking);
 MVXI int mvxi_job_packed_host(const job_t *J);
@@ -193,38 +201,40 @@ MVXI int mvxi_run_staged(mvx_comm_t *c, const job_t *J, hipStream_t st);
 MVXI int mvxi_typed_copy(mvx_comm_t *c, int dt, long n, const char *send, char *recv, hipStream_t st, int sync);
 MVXI void mvxi_stage_release(stage_res_t *S);
 
-/* ---- graphs of device calls (mvx_exec.c) ---------------------------------
+/* ---- graphs of device calls (mvx_graph.c) --------------------------------
  * With graphs on (mvx_comm_set_graphs), a device-buffer call whose job was
- * seen before is captured once into a HIP graph -- RCCL's transfer groups,
- * the combine launches, the cross-stream events of PIPE -- and replayed:
- * one hipGraphLaunch instead of the host issue of every group and kernel.
- * The key is everything the captured work depends on: the plan, the
- * buffers, the stream, the staging pool and the variant. */
+ * seen before is captured once into a HIP graph and replayed: one
+ * hipGraphLaunch instead of the host issue of every group and kernel.  The
+ * key is everything the captured work depends on. */
 #define GRAPH_CACHE 32
 typedef struct {
-    int state;                  /* 0 free, 1 seen once (ran eagerly; mvx_work.seen), 2 captured, 3 retired (mvx_exec.c) */
-    unsigned long long hash;
     mvx_plan plan;
     const char *send;
     char *recv;
     hipStream_t st;
-    char *pool;
-    int exch, slices, keep;
+    char *pool;                 /* the staging pool the work reads and writes */
+    int exch, slices, keep;     /* the variant and its slices; mvx_comm_t.keep */
+} graph_key_t;
+typedef struct {
+    int state;                  /* 0 free, 1 seen once (ran eagerly; mvx_work.seen), 2 captured, 3 retired */
+    unsigned long long hash;    /* of key */
+    graph_key_t key;
     hipGraphExec_t exec;
     int ran_exch;
     int forked;                 /* the graph has parallel branches (graph_forked) */
     hipEvent_t done;            /* recorded after each launch: the exec is idle once it completes */
     unsigned long stamp;
 } graph_ent_t;
-/* the communicator's staging pool grows to `need` bytes; graphs captured on
- * the old pool are destroyed (or retired) before it is freed (mvx_exec.c) */
-MVXI int mvxi_grow_pool(struct mvx_comm_t *c, size_t need);
-/* which graph execs may be destroyed mid-life on this HIP runtime (mvx_comm.c) */
+/* which graph execs may be destroyed mid-life on this HIP runtime */
 #define MVX_GRAPH_EVICT_NONE 0       /* none: retired, destroyed with the communicator */
 #define MVX_GRAPH_EVICT_SERIAL 1     /* those without parallel branches (HIP < 7.2) */
 #define MVX_GRAPH_EVICT_ALL 2        /* any (HIP >= 7.2) */
-MVXI int mvxi_graph_evict_default(void);
 
+MVXI void mvxi_graph_knobs(mvx_comm_t *c);      /* a new communicator's, from the environment */
+MVXI int mvxi_run_device(mvx_comm_t *c, const job_t *J, hipStream_t st);   /* eager, captured or replayed */
+MVXI void mvxi_graphs_unpool(mvx_comm_t *c);    /* c->pool is about to be freed (c->w set, no capture open) */
+MVXI void mvxi_graphs_clear(mvx_comm_t *c);     /* the communicator goes */
+MVXI void mvxi_gtrace(const char *what, int v); /* MVX_GRAPH_TRACE=1: a capture step on stderr */
 /* a capture is open on this thread: staging must not be reallocated */
 extern __thread int mvxi_capturing MVXI;
 
@@ -232,6 +242,7 @@ extern __thread int mvxi_capturing MVXI;
 /* The tables one call works in: formerly process statics, now owned by the
  * communicator (allocated at its first call, freed with it). */
 typedef struct mvx_work {
+    /* the first four are mvx_graph.c's alone */
     graph_ent_t graphs[GRAPH_CACHE];           /* captured device calls (live or retired) */
     graph_ent_t seen[GRAPH_CACHE];             /* jobs seen once (ran eagerly), the capture candidates */
     unsigned long graph_clock;
@@ -282,13 +293,15 @@ struct mvx_comm_t {
     int keep;                   /* this call's (op, type) is undefined: every combine keeps its inout */
     int ran_exch;               /* the variant the last call ran (mvx_comm_last_exchange), -1 none */
     hipStream_t last_st;        /* the stream of the last call (an abort's drain check) */
+    hipStream_t gstream;        /* PIPE's slices and graphs of null-stream calls run here (mvxi_null_fork / join) */
+    hipEvent_t gev[2];
+    /* graph state, read and written by mvx_graph.c alone */
     int graphs;                 /* mvx_comm_set_graphs: capture / replay device calls */
     int graph_cap;              /* graphs it may hold (MVX_GRAPH_CACHE, <= GRAPH_CACHE) */
     int graph_evict;            /* graphs destroyed mid-life (LRU, pool change): MVX_GRAPH_EVICT_* */
+    int graph_fork;             /* 0: PIPE's forked captures are off (MVX_GRAPH_FORK) */
     int graph_error;            /* a capture failed: graphs stay off on this communicator */
     int last_graph;             /* the last call: 0 eager, 1 replayed, 2 captured and launched */
-    hipStream_t gstream;        /* graphs of null-stream calls run here (fork / join) */
-    hipEvent_t gev[2];
     mvx_work *w;                /* per-call tables, NULL until the first call */
 };
 

@@ -402,6 +402,78 @@ static size_t span_bytes(const tspan_t *T, long n)
     return n > 0 ? (size_t)((n - 1) * T->ext + (T->hi - T->lo)) : 0;
 }
 
+/* ---- operand kinds and registration holds ---------------------------------
+ * Of a job's own buffers (mvxi_job_kinds) and of a packed job's host spans
+ * (packed_kinds below; the two re-ask lost registrations differently).
+ * mvxi_job_kinds: the buffers' kinds, one pointer query each (pageable ranges
+ * may come back pinned from the registration cache, held for the job until
+ * mvxi_job_release); returns 1 if any is host memory.  job_operand names
+ * operand q of the job (2r: send of rank r, 2r + 1: its recv). */
+static void job_operand(job_t *J, int q, const char **p, size_t *bytes, int **kind, unsigned long **hold)
+{
+    const int r = q >> 1;
+    const size_t E = (size_t)J->P[r].esize;
+    if (q & 1) { *p = J->recv[r]; *bytes = (size_t)J->nrecv[r] * E; *kind = &J->rkind[r]; *hold = &J->rhold[r]; }
+    else { *p = J->send[r]; *bytes = (size_t)J->nsend[r] * E; *kind = &J->skind[r]; *hold = &J->shold[r]; }
+}
+
+int mvxi_job_kinds(job_t *J)
+{
+    int r, host = 0;
+    if (!J->kinds) {
+        unsigned long *mine[2 * MVX_MAXP];
+        int q, nmine = 0, pass;
+        for (q = 0; q < 2 * J->nr; q++) {
+            const char *p;
+            size_t bytes;
+            int *kind;
+            unsigned long *hold;
+            job_operand(J, q, &p, &bytes, &kind, &hold);
+            *hold = 0;
+            *kind = bytes ? mvxi_buf_kind_hold(p, bytes, hold, mine, nmine) : MVX_BUF_DEVICE;
+            if (*hold) mine[nmine++] = hold;
+        }
+        /* an operand whose registration was merged into another's union and
+         * then lost (the union could not be registered) is asked again */
+        for (pass = 0; pass < 2 * J->nr; pass++) {
+            int again = 0;
+            for (q = 0; q < 2 * J->nr; q++) {
+                const char *p;
+                size_t bytes;
+                int *kind, i, n = 0;
+                unsigned long *hold, *others[2 * MVX_MAXP];
+                job_operand(J, q, &p, &bytes, &kind, &hold);
+                if (*kind != MVX_BUF_PINNED || *hold || !bytes || mvx_host_pinned(p) == 1) continue;
+                for (i = 0; i < nmine; i++)
+                    if (mine[i] != hold) others[n++] = mine[i];
+                *kind = mvxi_buf_kind_hold(p, bytes, hold, others, n);
+                if (*hold) {
+                    for (i = 0; i < nmine && mine[i] != hold; i++) ;
+                    if (i == nmine) mine[nmine++] = hold;
+                }
+                again = 1;
+            }
+            if (!again) break;
+        }
+        J->kinds = 1;
+    }
+    for (r = 0; r < J->nr; r++) host |= J->skind[r] != MVX_BUF_DEVICE || J->rkind[r] != MVX_BUF_DEVICE;
+    return host;
+}
+
+void mvxi_job_release(job_t *J, int rc)
+{
+    int r, any = 0;
+    if (!J->kinds) return;
+    for (r = 0; r < J->nr; r++) any |= J->shold[r] || J->rhold[r];
+    if (!any) return;
+    if (rc != MPI_SUCCESS && hipDeviceSynchronize() != hipSuccess) (void)hipGetLastError();
+    for (r = 0; r < J->nr; r++) {
+        mvxi_buf_release(J->shold[r]);
+        mvxi_buf_release(J->rhold[r]);
+        J->shold[r] = J->rhold[r] = 0;
+    }
+}
 
 /* the kinds of the host spans a packed job copies (the type maps' hull of
  * each host send / recv vector), with the registration cache's holds on

@@ -166,6 +166,36 @@ def main():
         report["hip_runtime"] = v.value          # the runtime this process runs on (torch's)
         side = torch.cuda.Stream()
         comm.set_graphs(True)
+        # the graph key holds PIPE's slice count: one job on one pair of
+        # buffers under 2 slices, then under 3 -- each triple eager, captured,
+        # replayed (a key without the slices would replay the 2-slice graph
+        # from the fourth call on).  First in the suite, while graph slots are
+        # free.  MPI_SUM on MPI_FLOAT, blocking; 4096 * world * 4 elements
+        # split into 2 and 3 slices at every world (256-element rounding of
+        # the slice length, span >= 4096 * 4), reported as ran_exch PIPE
+        tot = 4096 * world * 4
+        S = inputs(10, tot, None)
+        R0 = [np.zeros(tot, S[0].dtype) for q in range(world)]
+        rref = O.allreduce([x.view(np.uint8) for x in S], [x.view(np.uint8) for x in R0], tot, 10, 102)
+        sbuf = T.to_dev(S[rank])
+        rbuf = torch.zeros(tot * 4, dtype=torch.uint8, device="cuda")
+        report["graph_key_states"] = {}
+        for sl in (2, 3):
+            assert comm.set_exchange(mvx.EXCH_PIPE, sl) == 0
+            states = []
+            for rep in range(3):
+                rbuf.zero_()
+                torch.cuda.synchronize()
+                rc = mvx.MPI_Allreduce(sbuf, rbuf, tot, 10, 102, comm)
+                states.append(comm.last_graph()[0])
+                report["checked"] += 1
+                try:
+                    assert rc == rref[rank] == 0, (rc, rref[rank])
+                    assert comm.last_exchange() == mvx.EXCH_PIPE, comm.last_exchange()
+                    T.assert_same(102, 10, T.from_dev(rbuf)[: tot * 4], R0[rank], typemap_only=True)
+                except AssertionError as e:
+                    report["fails"].append(["ar key", 10, 102, tot, "pipe:%d" % sl, rep, str(e)[:200]])
+            report["graph_key_states"]["pipe:%d" % sl] = states
         only = os.environ.get("MVX_MP_MODES")       # e.g. "pipe": one variant only (diagnostics)
         for name, mode, sl in modes:
             if only and name not in only.split(","):

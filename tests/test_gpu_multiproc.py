@@ -170,9 +170,15 @@ def test_graphs_rccl_net(world):
         for key, runs in rep["graph_states"].items():
             # eager, captured, replayed -- or all eager once the
             # communicator holds its 32 graphs (none is destroyed before
-            # mvx_comm_free, csrc/mvx_exec.c)
+            # mvx_comm_free, csrc/mvx_graph.c)
             assert all(st in ([0, 2, 1], [0, 0, 0]) for st in runs), (key, runs)
         assert sum(st == [0, 2, 1] for runs in rep["graph_states"].values() for st in runs) >= 16
+        # the graph key holds PIPE's slice count: the same job on the same
+        # buffers under 2 and then 3 slices is eager, captured, replayed each
+        # time.  The rows above may also stay eager, but only once every slot
+        # holds a graph; this case runs first, with slots free, on any runtime
+        # (a forked capture is kept there, never refused)
+        assert rep["graph_key_states"] == {"pipe:2": [0, 2, 1], "pipe:3": [0, 2, 1]}, rep["graph_key_states"]
 
 
 @pytest.mark.parametrize("world", [2, 4])
@@ -181,7 +187,7 @@ def test_graphs_rccl_net_evicting(world):
     so graphs are destroyed mid-life: the least recently used one for each
     new job, and every one captured on a staging pool before the pool is
     reallocated -- on this process's HIP runtime (torch's 7.0) only graphs
-    without parallel branches, the forked ones being kept (csrc/mvx_exec.c,
+    without parallel branches, the forked ones being kept (csrc/mvx_graph.c,
     DESIGN.md section 6: HIP 7.0 crashes in hipGraphLaunch once forked
     graphs were destroyed).  Every result bit-exact, the cap held; a crash
     would print the native stack (MVX_SEGV_BT)."""
