@@ -32,6 +32,11 @@ extern "C" {
 #define MVX_FLOAT16            64   /* IEEE binary16 */
 #define MVX_BFLOAT16           65   /* the upper 16 bits of a binary32 */
 #endif
+/* and the two 8-bit OCP floating datatypes (the same block in mvx_mpi.h) */
+#ifndef MVX_FLOAT8_E4M3
+#define MVX_FLOAT8_E4M3        72   /* OCP e4m3fn: bias 7, no inf, NaN 0x7F / 0xFF, max 448 */
+#define MVX_FLOAT8_E5M2        73   /* OCP e5m2: bias 15, IEEE-style inf and NaN, max 57344 */
+#endif
 
 /* communicators: one process per GPU, collective over `size` processes.
  * Creation and every call on a communicator run on its device and leave the

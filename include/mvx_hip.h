@@ -46,7 +46,8 @@ extern "C" {
 
 /* 1 if a device kernel exists for (op, dtype); 0 otherwise.  dtype is a
  * reference handle, a derived one, or one of the extension types
- * MVX_FLOAT16 / MVX_BFLOAT16 (mvx_mpi.h), which have MPI_FLOAT's seven ops. */
+ * MVX_FLOAT16 / MVX_BFLOAT16 / MVX_FLOAT8_E4M3 / MVX_FLOAT8_E5M2 (mvx_mpi.h),
+ * which have MPI_FLOAT's seven ops. */
 int mvx_op_supported(int op, int dtype);
 /* Bytes of one element as the (op, dtype) kernel reads it (the C pair
  * struct for MAXLOC / MINLOC on a struct type), or 0 if undefined. */

@@ -92,6 +92,21 @@ typedef long MPI_Aint;      /* x86-64 LP64, the reference build's address int */
 #define MVX_BFLOAT16           65   /* the upper 16 bits of a binary32 */
 #endif
 
+/* EXTENSION beyond the reference ABI: the two 8-bit OCP floating types, as
+ * RCCL lists them.  Extent, size and alignment 1.  The ops are those of
+ * MPI_FLOAT, computed as for one more C floating type: every SUM / PROD step
+ * is the exact result rounded once (round-to-nearest-even) to the format,
+ * subnormals kept, overflow NOT saturated (E5M2: +-inf from a rounded
+ * magnitude of 61440; E4M3, which has no infinities: NaN above 448, the tie
+ * 464 rounding to 448); MAX / MIN as the selects of coll.h:14-19 on the
+ * decoded values, keeping the chosen operand's byte; the logical ops store
+ * 1.0 (0x38 / 0x3C) or 0.  Also defined, with the same
+ * values, in mvx_embed.h. */
+#ifndef MVX_FLOAT8_E4M3
+#define MVX_FLOAT8_E4M3        72   /* OCP e4m3fn: bias 7, no inf, NaN 0x7F / 0xFF, max 448 */
+#define MVX_FLOAT8_E5M2        73   /* OCP e5m2: bias 15, IEEE-style inf and NaN, max 57344 */
+#endif
+
 /* Ops: reference include/mpi.h:127-140 */
 #define MPI_OP_NULL ((MPI_Op)0)
 #define MPI_MAX     ((MPI_Op)100)

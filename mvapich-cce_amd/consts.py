@@ -19,6 +19,8 @@ MPI_CHARACTER = 1
 MPI_UNSIGNED_LONG_LONG = 35
 # EXTENSION beyond the reference ABI (include/mvx_mpi.h): the 16-bit floats
 MVX_FLOAT16, MVX_BFLOAT16 = 64, 65
+# and the 8-bit OCP floats (e4m3fn, e5m2)
+MVX_FLOAT8_E4M3, MVX_FLOAT8_E5M2 = 72, 73
 
 MPI_OP_NULL = 0
 MPI_MAX, MPI_MIN, MPI_SUM, MPI_PROD, MPI_LAND, MPI_BAND = 100, 101, 102, 103, 104, 105
@@ -66,6 +68,8 @@ NP_DTYPE = {
     MPI_2DOUBLE_PRECISION: PAIR_2DOUBLE, MPI_2COMPLEX: PAIR_2COMPLEX, MPI_2DOUBLE_COMPLEX: PAIR_2DCOMPLEX,
     # numpy has no bfloat16: its elements are uint16 bit patterns
     MVX_FLOAT16: np.dtype(np.float16), MVX_BFLOAT16: np.dtype(np.uint16),
+    # nor the 8-bit floats: uint8 bit patterns
+    MVX_FLOAT8_E4M3: np.dtype(np.uint8), MVX_FLOAT8_E5M2: np.dtype(np.uint8),
 }
 
 OP_NAMES = {MPI_MAX: "MPI_MAX", MPI_MIN: "MPI_MIN", MPI_SUM: "MPI_SUM", MPI_PROD: "MPI_PROD",
@@ -82,7 +86,8 @@ TYPE_NAMES = {MPI_CHAR: "MPI_CHAR", MPI_UNSIGNED_CHAR: "MPI_UNSIGNED_CHAR", MPI_
               MPI_DOUBLE_PRECISION: "MPI_DOUBLE_PRECISION", MPI_INTEGER: "MPI_INTEGER",
               MPI_2INTEGER: "MPI_2INTEGER", MPI_2COMPLEX: "MPI_2COMPLEX", MPI_2DOUBLE_COMPLEX: "MPI_2DOUBLE_COMPLEX",
               MPI_2REAL: "MPI_2REAL", MPI_2DOUBLE_PRECISION: "MPI_2DOUBLE_PRECISION",
-              MVX_FLOAT16: "MVX_FLOAT16", MVX_BFLOAT16: "MVX_BFLOAT16"}
+              MVX_FLOAT16: "MVX_FLOAT16", MVX_BFLOAT16: "MVX_BFLOAT16",
+              MVX_FLOAT8_E4M3: "MVX_FLOAT8_E4M3", MVX_FLOAT8_E5M2: "MVX_FLOAT8_E5M2"}
 
 # (op, type) pairs the reference defines (global_ops.c)
 _INTS = [MPI_CHAR, MPI_UNSIGNED_CHAR, MPI_SHORT, MPI_UNSIGNED_SHORT, MPI_INT, MPI_UNSIGNED, MPI_LONG,
@@ -103,6 +108,9 @@ DEFINED = {
 # the extension types: the seven ops of MPI_FLOAT (DEFINED stays the reference's table)
 _HALFS = [MVX_FLOAT16, MVX_BFLOAT16]
 DEFINED_EXT = {op: list(_HALFS) for op in (MPI_MAX, MPI_MIN, MPI_SUM, MPI_PROD, MPI_LAND, MPI_LOR, MPI_LXOR)}
+# the 8-bit floats, in a table of their own (DEFINED_EXT stays the 16-bit one)
+_FP8S = [MVX_FLOAT8_E4M3, MVX_FLOAT8_E5M2]
+DEFINED_EXT8 = {op: list(_FP8S) for op in DEFINED_EXT}
 DEVICE_TYPES = sorted(NP_DTYPE)
 
 # mvx_comm_set_call_kinds (include/mvx_embed.h)

@@ -78,6 +78,7 @@ static bool basic(int h, Type &t)
     };
     switch (h) {
     case MPI_CHAR: case MPI_UNSIGNED_CHAR: case MPI_BYTE: case MPI_PACKED: base(1); return true;
+    case MVX_FLOAT8_E4M3: case MVX_FLOAT8_E5M2: base(1); return true;  // extension (mvx_mpi.h)
     case MPI_SHORT: case MPI_UNSIGNED_SHORT: base(2); return true;
     case MVX_FLOAT16: case MVX_BFLOAT16: base(2); return true;     // extension (mvx_mpi.h)
     case MPI_INT: case MPI_UNSIGNED: case MPI_FLOAT: base(4); return true;

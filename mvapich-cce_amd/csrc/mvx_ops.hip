@@ -5,7 +5,7 @@
 // never touch the device or a buffer; run() is the one place that launches.
 // mvx_op_plan answers with the plan alone.  The kernels are in mvx_ops_kern.h
 // (design notes at its top), their host-side tables in mvx_ops_tab.h and
-// mvx_ops_{cmp,arith,logic,loc,half}.hip.
+// mvx_ops_{cmp,arith,logic,loc,half,fp8}.hip.
 #include <stdlib.h>
 
 #include "mvx_dtype.h"
@@ -90,6 +90,8 @@ static int ekind(int dtype)
     case MPI_LOGICAL: return EK_LOGICAL;
     case MVX_FLOAT16: return EK_F16;          // extension (mvx_mpi.h)
     case MVX_BFLOAT16: return EK_BF16;
+    case MVX_FLOAT8_E4M3: return EK_F8E4M3;
+    case MVX_FLOAT8_E5M2: return EK_F8E5M2;
     // the Fortran pairs: contiguous(2, x), the MAXLOC / MINLOC stride-2 case
     // of x's dte_type (global_ops.c:1387-1503); no case for COMPLEX (1498)
     case MPI_2INTEGER: return EK_PII;
@@ -113,6 +115,10 @@ static const KSet *lookup(int op, int dtype, int *rc)
     if (ek == EK_F16 || ek == EK_BF16) {
         if (op < MPI_MAX || op > MPI_MAXLOC) *rc = MPI_ERR_OP;
         return lookup_half(op, ek);
+    }
+    if (ek == EK_F8E4M3 || ek == EK_F8E5M2) {
+        if (op < MPI_MAX || op > MPI_MAXLOC) *rc = MPI_ERR_OP;
+        return lookup_fp8(op, ek);
     }
 
     switch (op) {

@@ -1,10 +1,12 @@
 #pragma once
 // mvx_ops_fn.h -- the ops of the MPI local reduction path on elements and on
 // chunks (what one lane moves per operand per step): element layouts, F<op, T>,
-// Chunk / CG, the chunk op CF with its SWAR and packed-16 forms.  Device code
-// only; the kernels that use them are in mvx_ops_kern.h (design notes there).
+// Chunk / CG, the chunk op CF with its SWAR, packed-16 and 8-bit float forms.
+// Device code only; the kernels that use them are in mvx_ops_kern.h (design
+// notes there).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "mvx_xf80.h"
 
@@ -399,6 +401,115 @@ template <int O> struct CF<O, f16> {
 };
 template <int O> struct CF<O, bf16> {
     static __device__ __forceinline__ void f(Chunk<bf16> &a, const Chunk<bf16> &b) { CF16<O, bf16>::f(a, b); }
+};
+
+// EXTENSION beyond the reference: the 8-bit OCP floating types MVX_FLOAT8_E4M3
+// (e4m3fn: bias 7, no infinities, NaN = 0x7F / 0xFF, largest finite 448) and
+// MVX_FLOAT8_E5M2 (bias 15, IEEE-style), as one more C floating type each
+// (DESIGN.md section 7).  gfx950 converts both natively: v_cvt_pk_f32_fp8 /
+// _bf8 widen the pair of bytes in either half of a word exactly, and
+// v_cvt_pk_fp8_f32 / _bf8_f32 narrow two f32 values round-to-nearest-even
+// into either half of a word, keeping the other half -- so a word of four
+// elements is never taken apart into bytes.  SUM / PROD work in f32 and narrow
+// after every step: the f32 sum or product of two 8-bit floats narrowed once
+// equals the directly rounded exact result (E4M3 sums and every product are
+// exact in f32; for E5M2 sums 24 >= 2 * 3 + 2).  Overflow is not saturated,
+// and the conversion itself sees to that: measured on the MI355X over all
+// 65,536 operand pairs of either format, SUM and PROD, it gives NaN for a
+// rounded E4M3 magnitude above 448 (the tie 464 goes to 448) and +-inf from
+// the E5M2 tie 61440 on, as the OCP non-saturating conversion does.  (The
+// ISA names one mode bit, FP16_OVFL, under which these conversions clamp
+// instead; a compiled kernel's descriptor leaves it clear and nothing here
+// writes mode registers.)  MAX / MIN compare the widened values and keep the
+// chosen operand's byte.  The logical ops never widen: a byte is zero iff its
+// seven magnitude bits are (-0 is zero, NaN is not), and they store 1.0
+// (0x38 / 0x3C) or 0.
+struct f8e4m3 { uint8_t u; };
+struct f8e5m2 { uint8_t u; };
+static_assert(sizeof(f8e4m3) == 1 && sizeof(f8e5m2) == 1, "");
+
+template <typename T> struct fp8 {
+    static constexpr bool e4m3 = std::is_same<T, f8e4m3>::value;
+    // both elements of one half of a word (hi: bytes 2 and 3), exactly
+    static __device__ __forceinline__ f32x2 widen(uint32_t w, bool hi)
+    {
+        if constexpr (e4m3) return hi ? __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true) : __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
+        else return hi ? __builtin_amdgcn_cvt_pk_f32_bf8((int)w, true) : __builtin_amdgcn_cvt_pk_f32_bf8((int)w, false);
+    }
+    // r narrowed into one half of `old`, the other half kept (v_cvt_pk_*_f32
+    // with op_sel)
+    static __device__ __forceinline__ uint32_t narrow(f32x2 r, uint32_t old, bool hi)
+    {
+        if constexpr (e4m3) return (uint32_t)(hi ? __builtin_amdgcn_cvt_pk_fp8_f32(r.x, r.y, (int)old, true) : __builtin_amdgcn_cvt_pk_fp8_f32(r.x, r.y, (int)old, false));
+        else return (uint32_t)(hi ? __builtin_amdgcn_cvt_pk_bf8_f32(r.x, r.y, (int)old, true) : __builtin_amdgcn_cvt_pk_bf8_f32(r.x, r.y, (int)old, false));
+    }
+};
+
+// per byte of a word of 8-bit floats: 1.0 where t has 0x80, else 0 (0x38 =
+// 0x40 - 0x08, 0x3C = 0x40 - 0x04: no borrow leaves a byte)
+template <typename T>
+__device__ __forceinline__ uint32_t fp8_truth(uint32_t t)
+{
+    return (t >> 1) - (t >> (fp8<T>::e4m3 ? 4 : 5));
+}
+
+// one word of four 8-bit floats; lanes: the bytes that count (the element
+// path passes one element in byte 0 and the rest of the word is ignored)
+template <int O, typename T>
+__device__ __forceinline__ uint32_t fp8_word(uint32_t a, uint32_t b)
+{
+    if constexpr (O == OLAND || O == OLOR || O == OLXOR) {
+        const uint32_t x = swar_nz(a & 0x7f7f7f7fu), y = swar_nz(b & 0x7f7f7f7fu);
+        return fp8_truth<T>(O == OLAND ? (x & y) : O == OLOR ? (x | y) : (x ^ y));
+    } else {
+        const f32x2 xl = fp8<T>::widen(a, false), xh = fp8<T>::widen(a, true);
+        const f32x2 yl = fp8<T>::widen(b, false), yh = fp8<T>::widen(b, true);
+        if constexpr (O == OSUM || O == OPROD) {
+            const f32x2 rl = O == OSUM ? xl + yl : xl * yl;
+            const f32x2 rh = O == OSUM ? xh + yh : xh * yh;
+            return fp8<T>::narrow(rh, fp8<T>::narrow(rl, 0u, false), true);
+        } else {
+            static_assert(O == OMAX || O == OMIN, "");
+            // coll.h:14-19 on the decoded values: b's byte where the compare
+            // holds (false for every NaN, and for -0 against +0), else a's
+            const bool t0 = O == OMAX ? (yl.x > xl.x) : (xl.x > yl.x), t1 = O == OMAX ? (yl.y > xl.y) : (xl.y > yl.y);
+            const bool t2 = O == OMAX ? (yh.x > xh.x) : (xh.x > yh.x), t3 = O == OMAX ? (yh.y > xh.y) : (xh.y > yh.y);
+            const uint32_t m = (t0 ? 0xffu : 0u) | (t1 ? 0xff00u : 0u) | (t2 ? 0xff0000u : 0u) | (t3 ? 0xff000000u : 0u);
+            return (a & ~m) | (b & m);
+        }
+    }
+}
+
+// the element path (heads, tails, mutually misaligned operands): the word op
+// on byte 0
+#define MVX_FP8_OP(O, T)                                                      \
+    template <> struct F<O, T> {                                              \
+        static __device__ __forceinline__ T f(T a, T b) { T r; r.u = (uint8_t)fp8_word<O, T>(a.u, b.u); return r; } \
+    };
+#define MVX_FP8_OPS(T)                                                        \
+    MVX_FP8_OP(OMAX, T) MVX_FP8_OP(OMIN, T) MVX_FP8_OP(OSUM, T) MVX_FP8_OP(OPROD, T) \
+    MVX_FP8_OP(OLAND, T) MVX_FP8_OP(OLOR, T) MVX_FP8_OP(OLXOR, T)
+MVX_FP8_OPS(f8e4m3) MVX_FP8_OPS(f8e5m2)
+#undef MVX_FP8_OPS
+#undef MVX_FP8_OP
+
+// the chunk stays in its four 32-bit words, 16 elements, as Chunk<uint8_t>
+template <> struct Chunk<f8e4m3> { uint32_t w[4]; };
+template <> struct Chunk<f8e5m2> { uint32_t w[4]; };
+
+template <int O, typename T>
+struct CFP8 {
+    static __device__ __forceinline__ void f(Chunk<T> &a, const Chunk<T> &b)
+    {
+#pragma unroll
+        for (int w = 0; w < 4; ++w) a.w[w] = fp8_word<O, T>(a.w[w], b.w[w]);
+    }
+};
+template <int O> struct CF<O, f8e4m3> {
+    static __device__ __forceinline__ void f(Chunk<f8e4m3> &a, const Chunk<f8e4m3> &b) { CFP8<O, f8e4m3>::f(a, b); }
+};
+template <int O> struct CF<O, f8e5m2> {
+    static __device__ __forceinline__ void f(Chunk<f8e5m2> &a, const Chunk<f8e5m2> &b) { CFP8<O, f8e5m2>::f(a, b); }
 };
 
 }  // namespace mvx

@@ -3,7 +3,7 @@
 // path and what they take (Params, BodyParams), written for gfx950 (CDNA4,
 // wave64).  The ops on elements and chunks are in mvx_ops_fn.h; the host-side
 // tables that name every instantiation are in mvx_ops_tab.h, which mvx_ops.hip
-// and the per-op table units mvx_ops_{cmp,arith,logic,loc,half}.hip include.
+// and the per-op table units mvx_ops_{cmp,arith,logic,loc,half,fp8}.hip include.
 // Built into libmvx_hip.so; C-ABI in include/mvx_hip.h.
 //
 // One kernel template covers every predefined op x type of the reference

@@ -3,7 +3,7 @@
 // (Config), the descriptor of one kernel instantiation (KVar), the families
 // and sets built from them, the element kinds and the per-op table units'
 // lookup functions.  Included by mvx_ops.hip (dispatch and launch policy) and
-// by mvx_ops_{cmp,arith,logic,loc,half}.hip, which instantiate the kernels of
+// by mvx_ops_{cmp,arith,logic,loc,half,fp8}.hip, which instantiate the kernels of
 // mvx_ops_kern.h through the macros below, one translation unit each so that
 // they compile in parallel.
 #include <stdio.h>
@@ -216,8 +216,8 @@ enum { EK_NONE = 0, EK_I8, EK_U8, EK_BYTE, EK_I16, EK_U16, EK_I32, EK_U32,
        // derived contiguous types: count-2 pairs of one base, and the rest
        EK_PP8, EK_PP16, EK_PP64, EK_PPF, EK_PPD, EK_PPX, EK_DERIVED,
        EK_LOGICAL,
-       // extension: MVX_FLOAT16, MVX_BFLOAT16
-       EK_F16, EK_BF16 };
+       // extension: MVX_FLOAT16, MVX_BFLOAT16, MVX_FLOAT8_E4M3, MVX_FLOAT8_E5M2
+       EK_F16, EK_BF16, EK_F8E4M3, EK_F8E5M2 };
 
 // Integer SUM/PROD/logical/bitwise results do not depend on signedness in
 // two's complement, so those share the unsigned kernel of the same width;
@@ -233,6 +233,9 @@ enum { EK_NONE = 0, EK_I8, EK_U8, EK_BYTE, EK_I16, EK_U16, EK_I32, EK_U32,
 #define HALFS(O, NAME)                                                       \
     case EK_F16:  { static KSet s = kset<O, f16>(NAME "_f16"); return &s; }  \
     case EK_BF16: { static KSet s = kset<O, bf16>(NAME "_bf16"); return &s; }
+#define FP8S(O, NAME)                                                        \
+    case EK_F8E4M3: { static KSet s = kset<O, f8e4m3>(NAME "_f8e4m3"); return &s; } \
+    case EK_F8E5M2: { static KSet s = kset<O, f8e5m2>(NAME "_f8e5m2"); return &s; }
 #define CMPLX(O, NAME)                                                       \
     case EK_C32: { static KSet s = kset<O, cf32>(NAME "_c32"); return &s; }  \
     case EK_C64: { static KSet s = kset<O, cf64>(NAME "_c64"); return &s; }
@@ -274,5 +277,6 @@ const KSet *lookup_logic(int op, int ek);   // L* and B* ops      mvx_ops_logic.
 int flog_sync();                            // MPI_LOGICAL's words on this device (mvx_ops_logic.hip)
 const KSet *lookup_loc(int op, int ek);     // MAXLOC, MINLOC     mvx_ops_loc.hip
 const KSet *lookup_half(int op, int ek);    // every op on the 16-bit floats  mvx_ops_half.hip
+const KSet *lookup_fp8(int op, int ek);     // every op on the 8-bit floats   mvx_ops_fp8.hip
 
 }  // namespace mvx

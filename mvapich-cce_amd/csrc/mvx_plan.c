@@ -162,7 +162,8 @@ int mvx_plan_algorithm_tuned(int coll, int p, long total, int dtype, int kind,
 static int is_ieee(int t)
 {
     return t == MPI_FLOAT || t == MPI_DOUBLE || t == MPI_LONG_DOUBLE || t == MPI_REAL ||
-           t == MPI_DOUBLE_PRECISION || t == MVX_FLOAT16 || t == MVX_BFLOAT16;
+           t == MPI_DOUBLE_PRECISION || t == MVX_FLOAT16 || t == MVX_BFLOAT16 ||
+           t == MVX_FLOAT8_E4M3 || t == MVX_FLOAT8_E5M2;
 }
 
 static int op_symmetric(int op, int dtype)

@@ -15,7 +15,8 @@ Prints one JSON line per config: algorithmic bytes, kernel time (HIP events on
 the launch stream), GB/s and fraction of the 8 TB/s HBM peak.
 
 Modes (arguments): sweep, all, all-tree, ks, x87 add lines to the four
-configs; half runs only the 16-bit floating types against MPI_SHORT.
+configs; half runs only the 16-bit floating types against MPI_SHORT, fp8 only
+the 8-bit ones against MPI_UNSIGNED_CHAR.
 """
 import importlib
 import json
@@ -103,8 +104,24 @@ def half(mvx):
             run(mvx, "H8-%s-%s" % (on, tn), op, t, 8, 0, 32 * MIB, 4, reps=10, warm=2)
 
 
+def fp8(mvx):
+    """The 8-bit floating extension types next to MPI_UNSIGNED_CHAR (the
+    sum_u8 / max_u8 SWAR kernels): the same shapes, ops and reasoning as
+    half() -- the same bytes at the same element width, so the lines differ by
+    the arithmetic alone.  The types are interleaved config by config."""
+    types = ((mvx.MVX_FLOAT8_E4M3, "e4m3"), (mvx.MVX_FLOAT8_E5M2, "e5m2"), (mvx.MPI_UNSIGNED_CHAR, "uchar"))
+    for op, on in ((mvx.MPI_SUM, "sum"), (mvx.MPI_MAX, "max")):
+        for t, tn in types:
+            run(mvx, "F2-%s-%s" % (on, tn), op, t, 2, 1, 256 * MIB, 4, reps=10, warm=2)
+        for t, tn in types:
+            run(mvx, "F8-%s-%s" % (on, tn), op, t, 8, 0, 32 * MIB, 4, reps=10, warm=2)
+
+
 def main():
     mvx = importlib.import_module("mvapich-cce_amd")
+    if "fp8" in sys.argv[1:]:
+        fp8(mvx)
+        return
     if "half" in sys.argv[1:]:      # on its own: the BASELINE configs are not repeated
         half(mvx)
         return
