@@ -427,6 +427,12 @@ typedef struct mvx_plan {
 /* The single-launch masks (mvx_op_program) of a plan's program when
  * k <= MVX_COMBINE_KMAX; returns 0, or MPI_ERR_ARG for a larger k. */
 int mvx_plan_masks(const mvx_plan *plan, unsigned *tree_mask, unsigned *chain_mask);
+/* A predefined-op program over more than MVX_COMBINE_KMAX leaves runs as
+ * several launches through scratch slots: *budget, the slots the executor
+ * reserves for the plan, and *used, the slots its launches take (a dry run of
+ * the executor: nothing is launched, no device is needed).  Both 0 up to
+ * MVX_COMBINE_KMAX leaves.  MPI_ERR_INTERN if the dry run itself fails. */
+int mvx_plan_wide_slots(const mvx_plan *plan, int *budget, int *used);
 
 /* Builds rank `rank`'s plan; returns 0 or an MPI error class. */
 int mvx_plan_build(mvx_plan *plan, int coll, int p, int rank, long count,

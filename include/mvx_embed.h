@@ -37,6 +37,12 @@ extern "C" {
 #define MVX_FLOAT8_E4M3        72   /* OCP e4m3fn: bias 7, no inf, NaN 0x7F / 0xFF, max 448 */
 #define MVX_FLOAT8_E5M2        73   /* OCP e5m2: bias 15, IEEE-style inf and NaN, max 57344 */
 #endif
+/* and the two f32-accumulating op handles defined on those four datatypes
+ * alone (the same block in mvx_mpi.h); the shim never translates to them */
+#ifndef MVX_SUM_ACC32
+#define MVX_SUM_ACC32         164   /* SUM, accumulated in f32, one rounding */
+#define MVX_PROD_ACC32        165   /* PROD, accumulated in f32, one rounding */
+#endif
 
 /* communicators: one process per GPU, collective over `size` processes.
  * Creation and every call on a communicator run on its device and leave the

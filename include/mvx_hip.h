@@ -47,7 +47,8 @@ extern "C" {
 /* 1 if a device kernel exists for (op, dtype); 0 otherwise.  dtype is a
  * reference handle, a derived one, or one of the extension types
  * MVX_FLOAT16 / MVX_BFLOAT16 / MVX_FLOAT8_E4M3 / MVX_FLOAT8_E5M2 (mvx_mpi.h),
- * which have MPI_FLOAT's seven ops. */
+ * which have MPI_FLOAT's seven ops and, alone, the two extension ops
+ * MVX_SUM_ACC32 / MVX_PROD_ACC32. */
 int mvx_op_supported(int op, int dtype);
 /* Bytes of one element as the (op, dtype) kernel reads it (the C pair
  * struct for MAXLOC / MINLOC on a struct type), or 0 if undefined. */
@@ -161,6 +162,25 @@ int mvx_op_program(int op, int dtype, const void *const *srcs,
                    unsigned chain_mask, void *dst, size_t n, void *hip_stream);
 unsigned mvx_tree_mask(int k);
 unsigned mvx_chain_mask(int k);
+
+/* The same program for MVX_SUM_ACC32 / MVX_PROD_ACC32 (mvx_mpi.h) with one
+ * side in binary32, the pieces a program over more than MVX_COMBINE_KMAX
+ * leaves is cut into: its intermediates are f32 and nothing is narrowed
+ * before the end.
+ *   MVX_F32_OUT: leaves and fold partners of the narrow dtype, dst n floats
+ *                (the f32 value of the program, not narrowed); k = 1 widens
+ *                a leaf.
+ *   MVX_F32_IN : leaves n floats each (fold must be NULL or all NULL), dst
+ *                of the narrow dtype, the f32 result narrowed once.
+ * (Both sides f32 is MPI_SUM / MPI_PROD on MPI_FLOAT.)  f32 operands must be
+ * 4-byte aligned.  Return codes of mvx_op_program; MPI_ERR_ARG for another
+ * op, side or a misaligned f32 operand. */
+#define MVX_F32_OUT 1
+#define MVX_F32_IN  2
+int mvx_op_program_f32(int op, int dtype, const void *const *srcs,
+                       const void *const *fold, int k, unsigned tree_mask,
+                       unsigned chain_mask, void *dst, size_t n, int side,
+                       void *hip_stream);
 
 /* What mvx_op_program would launch for these arguments, without launching:
  * the same checks and return codes, then the kernel template as rocprofv3

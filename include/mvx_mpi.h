@@ -107,6 +107,22 @@ typedef long MPI_Aint;      /* x86-64 LP64, the reference build's address int */
 #define MVX_FLOAT8_E5M2        73   /* OCP e5m2: bias 15, IEEE-style inf and NaN, max 57344 */
 #endif
 
+/* EXTENSION beyond the reference ABI: two op handles, above the reference's
+ * last op (111) and below the first user op (200).  Defined on the four
+ * extension datatypes above and on nothing else (329 elsewhere, derived forms
+ * of the four included).  Predefined, permanent, commutative, planned as
+ * MPI_SUM / MPI_PROD.  A result element is its block's whole combine program
+ * -- folds, tree steps, chain steps, in the plan's order and roles --
+ * evaluated in IEEE binary32 on the exactly widened operands (round to
+ * nearest even, subnormals kept, nothing fused) and narrowed ONCE to the
+ * format, by the narrowing MPI_SUM / MPI_PROD use after every step; the wire
+ * still carries 1- or 2-byte elements.  Also defined,
+ * with the same values, in mvx_embed.h. */
+#ifndef MVX_SUM_ACC32
+#define MVX_SUM_ACC32         164   /* SUM, accumulated in f32, one rounding */
+#define MVX_PROD_ACC32        165   /* PROD, accumulated in f32, one rounding */
+#endif
+
 /* Ops: reference include/mpi.h:127-140 */
 #define MPI_OP_NULL ((MPI_Op)0)
 #define MPI_MAX     ((MPI_Op)100)

@@ -78,6 +78,16 @@ class Plan(ctypes.Structure):
             raise ValueError("mvx_plan_masks rc=%d" % rc)
         return t.value, c.value
 
+    def wide_slots(self):
+        """(budget, used): the scratch slots the executor reserves for a
+        program over more than 8 leaves and the slots its launches take
+        (mvx_plan_wide_slots, a dry run)."""
+        b, u = ctypes.c_int(), ctypes.c_int()
+        rc = coll().mvx_plan_wide_slots(ctypes.byref(self), ctypes.byref(b), ctypes.byref(u))
+        if rc:
+            raise ValueError("mvx_plan_wide_slots rc=%d" % rc)
+        return b.value, u.value
+
     def segments(self):
         """[(start, end)] of the program's tree segments."""
         heads = [q for q in range(self.k) if self.seg_heads >> q & 1] + [self.k]
@@ -117,6 +127,7 @@ def _load():
     _hip.mvx_op_combine.argtypes = [i, i, pvp, pvp, i, i, vp, sz, vp]
     _hip.mvx_op_program.argtypes = [i, i, pvp, pvp, i, ctypes.c_uint, ctypes.c_uint, vp, sz, vp]
     _hip.mvx_op_plan.argtypes = [i, i, pvp, pvp, i, ctypes.c_uint, ctypes.c_uint, vp, sz, vp]
+    _hip.mvx_op_program_f32.argtypes = [i, i, pvp, pvp, i, ctypes.c_uint, ctypes.c_uint, vp, sz, i, vp]
     _hip.mvx_tree_mask.argtypes = [i]
     _hip.mvx_tree_mask.restype = ctypes.c_uint
     _hip.mvx_chain_mask.argtypes = [i]
@@ -188,6 +199,7 @@ def _load():
     c.mvx_reduce_scatter_multi.argtypes = [pvp, pvp, pi, i, i, i, pi, vp]
     c.mvx_plan_build.argtypes = [ctypes.POINTER(Plan), i, i, i, ctypes.c_long, pi, i, i, i]
     c.mvx_plan_masks.argtypes = [ctypes.POINTER(Plan), ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint)]
+    c.mvx_plan_wide_slots.argtypes = [ctypes.POINTER(Plan), pi, pi]
     c.mvx_plan_algorithm.argtypes = [i, i, ctypes.c_long, i]
     c.mvx_plan_build_kind.argtypes = [ctypes.POINTER(Plan), i, i, i, ctypes.c_long, pi, i, i, i, i]
     c.mvx_plan_algorithm_kind.argtypes = [i, i, ctypes.c_long, i, i]

@@ -10,7 +10,7 @@ from . import coll, hip
 from .consts import COLL_ALLREDUCE, COLL_REDUCE, COLL_REDUCE_SCATTER  # noqa: F401
 
 __all__ = [
-    "addr", "stream_handle", "op_apply", "op_combine", "op_program", "op_plan", "LaunchPlan", "Comm",
+    "addr", "stream_handle", "op_apply", "op_combine", "op_program", "op_program_f32", "op_plan", "LaunchPlan", "Comm",
     "MPI_Allreduce", "MPI_Reduce", "MPI_Reduce_scatter", "MPI_Scan", "MPI_Op_create", "MPI_Op_free", "op_create_device",
     "MPIR_call", "op_errno", "last_kernel", "last_kernel_symbol", "last_launch", "set_launch",
     "set_fortran_logical", "comm_reap", "host_register_enable", "host_unregister", "host_register_stats",
@@ -68,6 +68,15 @@ def op_program(op, dtype, srcs, dst, n, tree_mask, chain_mask, folds=None, strea
     fo = _pp(folds) if folds is not None else None
     return hip().mvx_op_program(op, dtype, _pp(srcs), fo, len(srcs), tree_mask, chain_mask, addr(dst), n,
                                 stream_handle(stream))
+
+
+def op_program_f32(op, dtype, srcs, dst, n, tree_mask, chain_mask, side, folds=None, stream=None):
+    """The combine program of MVX_SUM_ACC32 / MVX_PROD_ACC32 with one side in
+    float32 (mvx_op_program_f32): side F32_OUT, narrow leaves to an f32 dst,
+    not narrowed; side F32_IN, f32 leaves to a narrow dst, narrowed once."""
+    fo = _pp(folds) if folds is not None else None
+    return hip().mvx_op_program_f32(op, dtype, _pp(srcs), fo, len(srcs), tree_mask, chain_mask, addr(dst), n, side,
+                                    stream_handle(stream))
 
 
 class LaunchPlan(ctypes.Structure):

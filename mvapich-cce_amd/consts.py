@@ -25,6 +25,9 @@ MVX_FLOAT8_E4M3, MVX_FLOAT8_E5M2 = 72, 73
 MPI_OP_NULL = 0
 MPI_MAX, MPI_MIN, MPI_SUM, MPI_PROD, MPI_LAND, MPI_BAND = 100, 101, 102, 103, 104, 105
 MPI_LOR, MPI_BOR, MPI_LXOR, MPI_BXOR, MPI_MINLOC, MPI_MAXLOC = 106, 107, 108, 109, 110, 111
+# EXTENSION (include/mvx_mpi.h): SUM / PROD accumulated in f32 and narrowed once
+MVX_SUM_ACC32, MVX_PROD_ACC32 = 164, 165
+F32_OUT, F32_IN = 1, 2                       # mvx_op_program_f32's side (include/mvx_hip.h)
 
 MPI_COMM_WORLD, MPI_COMM_SELF = 91, 92
 
@@ -74,7 +77,8 @@ NP_DTYPE = {
 
 OP_NAMES = {MPI_MAX: "MPI_MAX", MPI_MIN: "MPI_MIN", MPI_SUM: "MPI_SUM", MPI_PROD: "MPI_PROD",
             MPI_LAND: "MPI_LAND", MPI_BAND: "MPI_BAND", MPI_LOR: "MPI_LOR", MPI_BOR: "MPI_BOR",
-            MPI_LXOR: "MPI_LXOR", MPI_BXOR: "MPI_BXOR", MPI_MINLOC: "MPI_MINLOC", MPI_MAXLOC: "MPI_MAXLOC"}
+            MPI_LXOR: "MPI_LXOR", MPI_BXOR: "MPI_BXOR", MPI_MINLOC: "MPI_MINLOC", MPI_MAXLOC: "MPI_MAXLOC",
+            MVX_SUM_ACC32: "MVX_SUM_ACC32", MVX_PROD_ACC32: "MVX_PROD_ACC32"}
 TYPE_NAMES = {MPI_CHAR: "MPI_CHAR", MPI_UNSIGNED_CHAR: "MPI_UNSIGNED_CHAR", MPI_BYTE: "MPI_BYTE",
               MPI_SHORT: "MPI_SHORT", MPI_UNSIGNED_SHORT: "MPI_UNSIGNED_SHORT", MPI_INT: "MPI_INT",
               MPI_UNSIGNED: "MPI_UNSIGNED", MPI_LONG: "MPI_LONG", MPI_UNSIGNED_LONG: "MPI_UNSIGNED_LONG",
@@ -111,6 +115,8 @@ DEFINED_EXT = {op: list(_HALFS) for op in (MPI_MAX, MPI_MIN, MPI_SUM, MPI_PROD, 
 # the 8-bit floats, in a table of their own (DEFINED_EXT stays the 16-bit one)
 _FP8S = [MVX_FLOAT8_E4M3, MVX_FLOAT8_E5M2]
 DEFINED_EXT8 = {op: list(_FP8S) for op in DEFINED_EXT}
+# the two f32-accumulating ops: the four narrow floats and nothing else
+DEFINED_ACC32 = {op: _HALFS + _FP8S for op in (MVX_SUM_ACC32, MVX_PROD_ACC32)}
 DEVICE_TYPES = sorted(NP_DTYPE)
 
 # mvx_comm_set_call_kinds (include/mvx_embed.h)

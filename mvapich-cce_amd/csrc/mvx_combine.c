@@ -2,9 +2,10 @@
  * mvx_combine.c -- phase B of a plan: one rank's combine program in the
  * reference's order.  Predefined ops on <= 8 leaves are one kernel launch
  * (mvx_op_program, libmvx_hip.so); wider programs run as groups of 8 with the
- * same association; user functions get the reference's operand roles
- * (host MPI_User_functions through pinned scratch, device functions in
- * HBM); datatypes with holes are unpacked to the extent layout the op sees.
+ * same association (the f32-accumulating extension ops through f32
+ * temporaries, so nothing is narrowed before the end); user functions get
+ * the reference's operand roles (host MPI_User_functions through pinned
+ * scratch, device functions in HBM); datatypes with holes are unpacked to the extent layout the op sees.
  * Reference: the (*uop) calls of intra_fns_new.c (e.g. 5505-5512, 5681-5699)
  * and global_ops.c.
  */
@@ -112,25 +113,60 @@ static int combine_user(mvx_comm_t *c, const mvx_plan *P, const void *const *src
  * truncated group tree is the truncated tree's restriction (q + 2^l < m
  * within the last group), so the association is the reference's.  A CHAIN
  * runs in windows of 8 whose result is the next window's first value. */
-typedef struct { const void *p, *f; } leafref;
+typedef struct { const void *p, *f; int wide; } leafref;   /* wide: an f32 temporary */
 
+/* (a scratch without a base is a dry run: slots are counted, nothing is
+ * launched -- mvx_plan_wide_slots) */
 static char *scratch_take(scratch_t *S)
 {
-    return S->used < S->cap ? S->base + S->slot * (size_t)S->used++ : NULL;
+    if (S->used >= S->cap) return NULL;
+    S->used++;
+    return S->base ? S->base + S->slot * (size_t)(S->used - 1) : (char *)S;
 }
 
-static int launch_prog(const mvx_plan *P, const leafref *v, int m, unsigned tmask,
-                       unsigned cmask, void *dst, hipStream_t st)
+/* The f32-accumulating ops (MVX_SUM_ACC32 / MVX_PROD_ACC32) keep every
+ * intermediate in f32: a temporary holds c_cnt floats, and a launch has its
+ * leaves all narrow or all f32.  Narrow leaves to an f32 temporary and f32
+ * leaves to the narrow result are the two forms of mvx_op_program_f32; f32
+ * to f32 is MPI_SUM / MPI_PROD on MPI_FLOAT, the same binary32 step.  A raw
+ * leaf that meets f32 values is first widened (with its fold partner) into
+ * a temporary of its own by a 1-leaf launch.  mvxi_wide_temps has the slot
+ * for it: a raw leaf reaches a later round only as the single trailing leaf
+ * of a tree's first round or as a one-leaf segment among the chain's heads,
+ * and either is counted there as a group or a segment that takes none. */
+static int launch_prog(const mvx_plan *P, leafref *v, int m, unsigned tmask,
+                       unsigned cmask, void *dst, int dst_wide, scratch_t *S, hipStream_t st)
 {
     const void *srcs[MVX_COMBINE_KMAX], *fold[MVX_COMBINE_KMAX];
-    int q;
+    const size_t n = (size_t)P->c_cnt;
+    int q, nw = 0, rc;
     if (!dst) return MPI_ERR_INTERN;
+    for (q = 0; q < m; q++) nw += v[q].wide;
+    if (nw || dst_wide) {
+        if (!mvxi_acc32(P->op)) return MPI_ERR_INTERN;
+        for (q = 0; nw && q < m; q++) {
+            char *t;
+            if (v[q].wide) continue;
+            if (!(t = scratch_take(S))) return MPI_ERR_INTERN;
+            if (S->base && (rc = mvx_op_program_f32(P->op, P->dtype, &v[q].p, &v[q].f, 1, 0u, 0u, t, n, MVX_F32_OUT, st)))
+                return rc;
+            v[q].p = t; v[q].f = NULL; v[q].wide = 1;
+        }
+    }
     for (q = 0; q < m; q++) { srcs[q] = v[q].p; fold[q] = v[q].f; }
-    return mvx_op_program(P->op, P->dtype, srcs, fold, m, tmask, cmask, dst, (size_t)P->c_cnt, st);
+    if (!S->base) return MPI_SUCCESS;
+    if (!nw && !dst_wide) return mvx_op_program(P->op, P->dtype, srcs, fold, m, tmask, cmask, dst, n, st);
+    if (!nw) return mvx_op_program_f32(P->op, P->dtype, srcs, fold, m, tmask, cmask, dst, n, MVX_F32_OUT, st);
+    if (!dst_wide) return mvx_op_program_f32(P->op, P->dtype, srcs, NULL, m, tmask, cmask, dst, n, MVX_F32_IN, st);
+    return mvx_op_program(P->op == MVX_SUM_ACC32 ? MPI_SUM : MPI_PROD, MPI_FLOAT, srcs, NULL, m, tmask, cmask, dst,
+                          n, st);
 }
 
-static int tree_eval(const mvx_plan *P, leafref *v, int m, void *dst, scratch_t *S, hipStream_t st)
+/* dst_wide: dst takes the f32 value (a temporary of an f32-accumulating op) */
+static int tree_eval(const mvx_plan *P, leafref *v, int m, void *dst, int dst_wide, scratch_t *S,
+                     hipStream_t st)
 {
+    const int acc = mvxi_acc32(P->op);
     int rc;
     while (m > MVX_COMBINE_KMAX) {
         const int ng = (m + 7) / 8;
@@ -140,24 +176,25 @@ static int tree_eval(const mvx_plan *P, leafref *v, int m, void *dst, scratch_t 
             char *t;
             if (len == 1 && !v[8 * g].f) { v[g] = v[8 * g]; continue; }
             t = scratch_take(S);
-            if ((rc = launch_prog(P, v + 8 * g, len, mvx_tree_mask(len), 0u, t, st))) return rc;
-            v[g].p = t; v[g].f = NULL;
+            if ((rc = launch_prog(P, v + 8 * g, len, mvx_tree_mask(len), 0u, t, acc, S, st))) return rc;
+            v[g].p = t; v[g].f = NULL; v[g].wide = acc;
         }
         m = ng;
     }
-    return launch_prog(P, v, m, mvx_tree_mask(m), 0u, dst, st);
+    return launch_prog(P, v, m, mvx_tree_mask(m), 0u, dst, dst_wide, S, st);
 }
 
 static int chain_eval(const mvx_plan *P, leafref *v, int m, void *dst, scratch_t *S, hipStream_t st)
 {
+    const int acc = mvxi_acc32(P->op);
     int i = 0, rc;
     while (m - i > MVX_COMBINE_KMAX) {
         char *t = scratch_take(S);
-        if ((rc = launch_prog(P, v + i, 8, 0u, mvx_chain_mask(8), t, st))) return rc;
+        if ((rc = launch_prog(P, v + i, 8, 0u, mvx_chain_mask(8), t, acc, S, st))) return rc;
         i += 7;
-        v[i].p = t; v[i].f = NULL;
+        v[i].p = t; v[i].f = NULL; v[i].wide = acc;
     }
-    return launch_prog(P, v + i, m - i, 0u, mvx_chain_mask(m - i), dst, st);
+    return launch_prog(P, v + i, m - i, 0u, mvx_chain_mask(m - i), dst, 0, S, st);
 }
 
 /* scratch slots a >8-leaf program can take: per segment its group temps
@@ -179,17 +216,38 @@ static int combine_wide(const mvx_plan *P, const void *const *srcs, const void *
 {
     leafref v[MVX_MAXK], heads[MVX_MAXK];
     int q, s, e, nh = 0, rc;
-    for (q = 0; q < P->k; q++) { v[q].p = srcs[q]; v[q].f = fold[q]; }
-    if (seg_end(P, 0) == P->k) return tree_eval(P, v, P->k, dst, S, st);
+    for (q = 0; q < P->k; q++) { v[q].p = srcs[q]; v[q].f = fold[q]; v[q].wide = 0; }
+    if (seg_end(P, 0) == P->k) return tree_eval(P, v, P->k, dst, 0, S, st);
     for (s = 0; s < P->k; s = e) {
         e = seg_end(P, s);
         if (e - s == 1) { heads[nh++] = v[s]; continue; }
         heads[nh].p = scratch_take(S);
         heads[nh].f = NULL;
-        if ((rc = tree_eval(P, v + s, e - s, (void *)heads[nh].p, S, st))) return rc;
+        heads[nh].wide = mvxi_acc32(P->op);
+        if ((rc = tree_eval(P, v + s, e - s, (void *)heads[nh].p, heads[nh].wide, S, st))) return rc;
         nh++;
     }
     return chain_eval(P, heads, nh, dst, S, st);
+}
+
+/* The slots mvxi_wide_temps budgets for P's combine and the slots the
+ * executor above takes for it, by a dry run of the same code (nothing is
+ * launched, no device is needed). */
+int mvx_plan_wide_slots(const mvx_plan *P, int *budget, int *used)
+{
+    const void *srcs[MVX_MAXK], *fold[MVX_MAXK];
+    scratch_t S;
+    char dst;
+    int q, rc = MPI_SUCCESS;
+    if (!P || !budget || !used) return MPI_ERR_ARG;
+    *budget = mvxi_wide_temps(P);
+    *used = 0;
+    if (P->k <= MVX_COMBINE_KMAX) return MPI_SUCCESS;
+    for (q = 0; q < P->k; q++) { srcs[q] = &dst; fold[q] = P->leaf_fold[q] >= 0 ? &dst : NULL; }
+    S.base = NULL; S.slot = 0; S.used = 0; S.cap = 1 << 20;
+    rc = combine_wide(P, srcs, fold, &dst, &S, NULL);
+    *used = S.used;
+    return rc;
 }
 
 /* ---- datatypes with holes (plan->packed) --------------------------------

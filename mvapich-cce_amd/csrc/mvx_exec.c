@@ -34,8 +34,8 @@ static size_t exec_layout(rank_exec_t *X)
     X->wide_n = P->has_combine ? mvxi_wide_temps(P) : 0;
     X->wide_off = X->wide_slot = 0;
     if (X->wide_n) {
-        X->wide_off = slot_at(need, like);
-        X->wide_slot = ((size_t)(P->c_cnt * E) + SLOT_STAGGER + 255) & ~(size_t)255;
+        X->wide_off = al256(need) + mvxi_wide_residue(P, like);
+        X->wide_slot = ((size_t)P->c_cnt * mvxi_wide_esize(P) + SLOT_STAGGER + 255) & ~(size_t)255;
         need = X->wide_off + X->wide_slot * (size_t)X->wide_n;
     }
     return need;
@@ -457,15 +457,16 @@ static int run_device_coll(mvx_comm_t *c, const job_t *J, long b, hipStream_t st
     X.P = P; X.c = c; X.sendbuf = J->send[0]; X.recvbuf = J->recv[0];
     stage = al256(bb * (size_t)P->p);
     X.wide_n = mvxi_wide_temps(P);
-    X.wide_slot = al256(bb + SLOT_STAGGER);
-    if ((rc = mvxi_grow_pool(c, stage + X.wide_slot * (size_t)X.wide_n))) return rc;
+    X.wide_slot = al256((size_t)b * mvxi_wide_esize(P) + SLOT_STAGGER);
+    X.wide_off = stage + (mvxi_acc32(P->op) ? mvxi_wide_residue(P, J->send[0]) : 0);
+    if ((rc = mvxi_grow_pool(c, X.wide_off + X.wide_slot * (size_t)X.wide_n))) return rc;
     c->ran_exch = MVX_EXCH_COLL;
     if ((rc = mvxi_tev(c, 0, st))) return rc;
     if ((rc = t->alltoall(t, J->send[0], c->pool, bb, st))) return rc;
     if ((rc = mvxi_tev(c, 1, st))) return rc;
     for (s = 0; s < P->p; s++)
         leafp[s] = s == P->rank ? J->send[0] + (size_t)P->rank * bb : c->pool + (size_t)s * bb;
-    S.base = c->pool + stage; S.slot = X.wide_slot; S.used = 0; S.cap = X.wide_n;
+    S.base = c->pool + X.wide_off; S.slot = X.wide_slot; S.used = 0; S.cap = X.wide_n;
     if ((rc = mvxi_combine(c, P, leafp, J->recv[0] + P->c_dst_off * P->esize, &S, st))) return rc;
     if ((rc = mvxi_tev(c, 2, st))) return rc;
     if (P->coll == MVX_COLL_ALLREDUCE && (rc = t->allgather(t, J->recv[0], bb, st))) return rc;

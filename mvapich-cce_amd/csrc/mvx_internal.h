@@ -331,6 +331,8 @@ typedef struct {           /* struct MPIR_OP, include/mpiops.h:1-11 */
 } mvx_op_t;
 
 MVXI int mvxi_predefined(MPI_Op op);
+/* the extension ops MVX_SUM_ACC32 / MVX_PROD_ACC32 (predefined too) */
+static inline int mvxi_acc32(MPI_Op op) { return op == MVX_SUM_ACC32 || op == MVX_PROD_ACC32; }
 MVXI mvx_op_t *mvxi_user_op(MPI_Op op);
 MVXI int mvxi_op_kind(MPI_Op op);
 MVXI int mvxi_op_verdict(MPI_Op op, MPI_Datatype dt);
@@ -341,6 +343,19 @@ MVXI int mvxi_is_device_ptr(const void *p);
 typedef struct { char *base; size_t slot; int used, cap; } scratch_t;
 /* scratch slots a > 8-leaf program can take (0 up to MVX_COMBINE_KMAX) */
 MVXI int mvxi_wide_temps(const mvx_plan *P);
+/* bytes per element of those slots (the f32-accumulating ops keep their
+ * intermediates in f32), and a slot's base offset past a 256-byte boundary
+ * for leaves aligned like `like`: the leaves' own residue mod 16, or for f32
+ * slots the one that puts the first whole word of narrow elements on a
+ * 16-byte boundary of the floats (mvx_ops.hip: split, split_f32) */
+static inline size_t mvxi_wide_esize(const mvx_plan *P) { return mvxi_acc32(P->op) ? 4 : (size_t)P->esize; }
+static inline size_t mvxi_wide_residue(const mvx_plan *P, const void *like)
+{
+    size_t head;
+    if (!mvxi_acc32(P->op)) return (uintptr_t)like & 15;
+    head = ((4 - ((uintptr_t)like & 3)) & 3) / (size_t)P->esize;
+    return (16 - 4 * head) & 15;
+}
 MVXI int mvxi_combine(mvx_comm_t *c, const mvx_plan *P, const char *const *leafp, void *dst,
                       scratch_t *S, hipStream_t st);
 

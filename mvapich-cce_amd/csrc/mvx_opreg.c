@@ -13,7 +13,7 @@
 #define OP_COOKIE 0xca01beafu
 static mvx_op_t g_user_ops[MAX_USER_OPS];
 
-int mvxi_predefined(MPI_Op op) { return op >= MPI_MAX && op <= MPI_MAXLOC; }
+int mvxi_predefined(MPI_Op op) { return (op >= MPI_MAX && op <= MPI_MAXLOC) || mvxi_acc32(op); }
 
 mvx_op_t *mvxi_user_op(MPI_Op op)
 {

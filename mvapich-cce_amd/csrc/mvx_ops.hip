@@ -5,7 +5,7 @@
 // never touch the device or a buffer; run() is the one place that launches.
 // mvx_op_plan answers with the plan alone.  The kernels are in mvx_ops_kern.h
 // (design notes at its top), their host-side tables in mvx_ops_tab.h and
-// mvx_ops_{cmp,arith,logic,loc,half,fp8}.hip.
+// mvx_ops_{cmp,arith,logic,loc,half,fp8,acc32}.hip.
 #include <stdlib.h>
 
 #include "mvx_dtype.h"
@@ -105,11 +105,16 @@ static int ekind(int dtype)
 // Returns the kernel set, or NULL with *rc set to the reference's answer for
 // that (op, type): 329 where the op's switch has no case for it
 // (global_ops.c:158-161 and every sibling default), and MPI_ERR_OP for a
-// handle outside MPI_MAX..MPI_MAXLOC.
+// handle outside MPI_MAX..MPI_MAXLOC that is not one of the two extension
+// ops.  Those (MVX_SUM_ACC32, MVX_PROD_ACC32) have a case for the four
+// narrow floating types alone.
+static bool acc32(int op) { return op == MVX_SUM_ACC32 || op == MVX_PROD_ACC32; }
+
 static const KSet *lookup(int op, int dtype, int *rc)
 {
     int ek = ekind(dtype);
     *rc = MVX_ERR_OP_NOT_DEFINED;
+    if (acc32(op)) return lookup_acc32(op, ek);
     if (ek == EK_LOGICAL && (op == MPI_BAND || op == MPI_BOR || op == MPI_BXOR))
         ek = EK_U32;                 // bitwise on the MPI_Fint word
     if (ek == EK_F16 || ek == EK_BF16) {
@@ -345,6 +350,50 @@ static int program_params(int op, int dtype, const void *const *srcs, const void
     return MPI_SUCCESS;
 }
 
+// The one-side-f32 program (k_combine_f32).  The narrow operands -- the
+// leaves and fold partners (f32_out), or the destination -- must share their
+// residue mod 4 with a whole number of elements up to the next word; `head`
+// elements then lead to `nvec` words of L elements, provided every f32
+// operand is 4 * L-byte aligned from element `head` on.  Otherwise every
+// element goes alone.
+static Split split_f32(const Params &P, int esize, bool f32_out)
+{
+    const int L = 4 / esize;
+    const uintptr_t m = (uintptr_t)(f32_out ? P.src[0] : P.dst) & 3;
+    const long pre = (long)((4 - m) & 3);
+    if (pre % esize != 0) return {0, 0, 0};
+    const long head = pre / esize < P.n ? pre / esize : P.n;
+    const uintptr_t fa = (uintptr_t)(4 * L - 1);
+    if (f32_out) {
+        for (int q = 0; q < P.k; ++q)
+            if (((uintptr_t)P.src[q] & 3) != m || (P.fold[q] && ((uintptr_t)P.fold[q] & 3) != m)) return {0, 0, 0};
+        if (((uintptr_t)P.dst + 4 * (uintptr_t)head) & fa) return {0, 0, 0};
+    } else {
+        for (int q = 0; q < P.k; ++q)
+            if (((uintptr_t)P.src[q] + 4 * (uintptr_t)head) & fa) return {0, 0, 0};
+    }
+    return {head, (P.n - head) / L, 1};
+}
+
+static Plan plan_f32(const KSet *ks, Params &P, bool f32_out, const Config &cfg)
+{
+    const KVar &V = ks->f32side[f32_out ? 0 : 1];
+    const Split s = split_f32(P, ks->esize, f32_out);
+    P.head = s.head;
+    P.nvec = s.nvec;
+    P.vec_ok = s.vec_ok;
+    long work = ((s.vec_ok ? s.nvec : P.n) + 255) / 256;
+    if (work < 1) work = 1;
+    Plan pl;
+    pl.fn = V.fn;
+    pl.name = V.name;
+    snprintf(pl.tag, sizeof pl.tag, "%s_k%d_%s", ks->name, P.k, f32_out ? "to_f32" : "from_f32");
+    pl.blocks = (unsigned)(work < cfg.block_cap ? work : cfg.block_cap);
+    pl.lds = 0;
+    pl.body = false;
+    return pl;
+}
+
 }  // namespace mvx
 
 using namespace mvx;
@@ -389,6 +438,25 @@ extern "C" int mvx_op_program(int op, int dtype, const void *const *srcs,
     const int rc = program_params(op, dtype, srcs, fold, k, tree_mask, chain_mask, dst, n, &ks, P);
     if (rc != MPI_SUCCESS || !ks) return rc;
     return run(plan_params(ks, P), P, (hipStream_t)stream);
+}
+
+extern "C" int mvx_op_program_f32(int op, int dtype, const void *const *srcs, const void *const *fold, int k,
+                                  unsigned tree_mask, unsigned chain_mask, void *dst, size_t n, int side,
+                                  void *stream)
+{
+    const KSet *ks;
+    Params P;
+    const int rc = program_params(op, dtype, srcs, fold, k, tree_mask, chain_mask, dst, n, &ks, P);
+    if (rc != MPI_SUCCESS) return rc;
+    /* only the f32-accumulating ops have an f32 side */
+    if (!acc32(op) || (side != MVX_F32_OUT && side != MVX_F32_IN)) return MPI_ERR_ARG;
+    if (!ks) return MPI_SUCCESS;
+    /* f32 operands are floats: 4-byte aligned; f32 leaves are never folded */
+    for (int q = 0; q < k; ++q) {
+        if (side == MVX_F32_IN && (P.fold[q] || ((uintptr_t)P.src[q] & 3))) return MPI_ERR_ARG;
+    }
+    if (side == MVX_F32_OUT && ((uintptr_t)P.dst & 3)) return MPI_ERR_ARG;
+    return run(plan_f32(ks, P, side == MVX_F32_OUT, config()), P, (hipStream_t)stream);
 }
 
 extern "C" int mvx_op_plan(int op, int dtype, const void *const *srcs, const void *const *fold, int k,

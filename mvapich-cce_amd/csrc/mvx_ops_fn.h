@@ -2,8 +2,9 @@
 // mvx_ops_fn.h -- the ops of the MPI local reduction path on elements and on
 // chunks (what one lane moves per operand per step): element layouts, F<op, T>,
 // Chunk / CG, the chunk op CF with its SWAR, packed-16 and 8-bit float forms.
-// Device code only; the kernels that use them are in mvx_ops_kern.h (design
-// notes there).
+// Last, the wide accumulator of the f32-accumulating ops (Wide, acc_steps,
+// acc_chunk).  Device code only; the kernels that use them are in
+// mvx_ops_kern.h (design notes there).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
@@ -13,7 +14,10 @@
 namespace mvx {
 
 enum { OMAX = 0, OMIN, OSUM, OPROD, OLAND, OBAND, OLOR, OBOR, OLXOR, OBXOR,
-       OMINLOC, OMAXLOC };
+       OMINLOC, OMAXLOC,
+       // extension (MVX_SUM_ACC32 / MVX_PROD_ACC32): the whole combine program
+       // in binary32, narrowed once (the end of this file)
+       OSUMA, OPRODA };
 
 // Element layouts: the reference's C types on x86-64 LP64.
 struct cf32 { float re, im; };                          // global_ops.c:43-46
@@ -511,5 +515,171 @@ template <int O> struct CF<O, f8e4m3> {
 template <int O> struct CF<O, f8e5m2> {
     static __device__ __forceinline__ void f(Chunk<f8e5m2> &a, const Chunk<f8e5m2> &b) { CFP8<O, f8e5m2>::f(a, b); }
 };
+
+// EXTENSION beyond the reference: MVX_SUM_ACC32 / MVX_PROD_ACC32 on the four
+// narrow floating types.  A launch's whole combine
+// program -- folds, tree steps, chain steps -- runs on binary32 values: every
+// leaf is widened exactly, every step is one f32 add or multiply (round to
+// nearest even, subnormals kept, nothing fused: -ffp-contract=off), and the
+// result is narrowed once, by the narrowing the per-step ops use.  No narrow
+// value exists in between.  A chunk is evaluated one 32-bit word of each leaf
+// at a time -- Wide<T>::L f32 lanes per leaf, 4 for the 8-bit types and 2 for
+// the 16-bit ones -- so 8 leaves x U chunks stay within the registers the
+// per-step tree bodies use.
+template <int O> struct acc_op { static constexpr bool v = O == OSUMA || O == OPRODA; };
+
+template <int O>
+__device__ __forceinline__ float accf(float a, float b)
+{
+    static_assert(acc_op<O>::v, "");
+    return O == OSUMA ? a + b : a * b;
+}
+
+// one word of a chunk <-> its L elements as f32 lanes
+template <typename T> struct Wide;
+
+template <typename T> struct WideFP8 {
+    static constexpr int L = 4;
+    static __device__ __forceinline__ void widen(uint32_t w, float (&y)[4])
+    {
+        const f32x2 lo = fp8<T>::widen(w, false), hi = fp8<T>::widen(w, true);
+        y[0] = lo.x; y[1] = lo.y; y[2] = hi.x; y[3] = hi.y;
+    }
+    static __device__ __forceinline__ uint32_t narrow(const float (&y)[4])
+    {
+        f32x2 lo, hi;
+        lo.x = y[0]; lo.y = y[1]; hi.x = y[2]; hi.y = y[3];
+        return fp8<T>::narrow(hi, fp8<T>::narrow(lo, 0u, false), true);
+    }
+};
+template <> struct Wide<f8e4m3> : WideFP8<f8e4m3> {};
+template <> struct Wide<f8e5m2> : WideFP8<f8e5m2> {};
+
+template <> struct Wide<bf16> {
+    static constexpr int L = 2;
+    static __device__ __forceinline__ void widen(uint32_t w, float (&y)[2])
+    {
+        y[0] = bits_f32(w << 16);
+        y[1] = bits_f32(w & 0xffff0000u);
+    }
+    static __device__ __forceinline__ uint32_t narrow(const float (&y)[2])   // v_cvt_pk_bf16_f32
+    {
+        f32x2 r;
+        r.x = y[0]; r.y = y[1];
+        const bf16x2 h = __builtin_convertvector(r, bf16x2);
+        uint32_t w;
+        __builtin_memcpy(&w, &h, 4);
+        return w;
+    }
+};
+
+// f16: v_cvt_f32_f16 widens exactly (subnormals included); the pair of a
+// word narrows with one v_cvt_pk_f16_f32 (the element path's single value with
+// v_cvt_f16_f32), round-to-nearest-even under the kernel's default rounding
+// mode, to a subnormal, +-inf or a NaN where the value asks for one
+template <> struct Wide<f16> {
+    static constexpr int L = 2;
+    static __device__ __forceinline__ void widen(uint32_t w, float (&y)[2])
+    {
+        f16x2 h;
+        __builtin_memcpy(&h, &w, 4);
+        y[0] = (float)h.x;
+        y[1] = (float)h.y;
+    }
+    static __device__ __forceinline__ uint32_t narrow(const float (&y)[2])
+    {
+        f16x2 h;
+        h.x = (f16)y[0];
+        h.y = (f16)y[1];
+        uint32_t w;
+        __builtin_memcpy(&w, &h, 4);
+        return w;
+    }
+};
+
+// the element path: one element in lane 0 of a word
+template <typename T>
+__device__ __forceinline__ float widen_elt(const T *p)
+{
+    uint32_t w = 0;
+    __builtin_memcpy(&w, p, sizeof(T));
+    float y[Wide<T>::L];
+    Wide<T>::widen(w, y);
+    return y[0];
+}
+template <typename T>
+__device__ __forceinline__ void narrow_elt(T *p, float v)
+{
+    float y[Wide<T>::L] = {};
+    y[0] = v;
+    const uint32_t w = Wide<T>::narrow(y);
+    __builtin_memcpy(p, &w, sizeof(T));
+}
+
+// The combine program (mvx_ops_kern.h: reduce_leaves) on L f32 lanes per
+// leaf.  PROG = 1: the full balanced tree over KMAX leaves.
+template <int O, int KMAX, int L, int PROG>
+__device__ __forceinline__ void acc_steps(float (&y)[KMAX][L], int k, unsigned tree_mask, unsigned chain_mask)
+{
+    if constexpr (PROG == 1) {
+#pragma unroll
+        for (int h = 1; h < KMAX; h <<= 1)
+#pragma unroll
+            for (int q = 0; q + h < KMAX; q += 2 * h)
+#pragma unroll
+                for (int j = 0; j < L; ++j) y[q][j] = accf<O>(y[q][j], y[q + h][j]);
+    } else if constexpr (KMAX == 2) {
+        if (k == 2) {
+#pragma unroll
+            for (int j = 0; j < L; ++j) y[0][j] = accf<O>(y[0][j], y[1][j]);
+        }
+    } else {
+#pragma unroll
+        for (int l = 0; (1 << l) < KMAX; ++l) {
+#pragma unroll
+            for (int q = 0; q + (1 << l) < KMAX; ++q) {
+                if (tree_mask & (1u << (l * 8 + q))) {
+#pragma unroll
+                    for (int j = 0; j < L; ++j) y[q][j] = accf<O>(y[q][j], y[q + (1 << l)][j]);
+                }
+            }
+        }
+#pragma unroll
+        for (int q = 1; q < KMAX; ++q) {
+            if (chain_mask & (1u << q)) {
+#pragma unroll
+                for (int j = 0; j < L; ++j) y[0][j] = accf<O>(y[0][j], y[q][j]);
+            }
+        }
+    }
+}
+
+// One chunk of every leaf: x[0] = narrow(program(widen(x[q]) op widen(xf[q])
+// where fold_mask has bit q)), a word at a time.  Leaves q >= k are never
+// read (PROG = 1: k = KMAX).
+template <int O, typename T, int KMAX, int PROG>
+__device__ __forceinline__ void acc_chunk(Chunk<T> (&x)[KMAX], const Chunk<T> (&xf)[KMAX], unsigned fold_mask,
+                                          int k, unsigned tree_mask, unsigned chain_mask)
+{
+    constexpr int L = Wide<T>::L;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        float y[KMAX][L];
+#pragma unroll
+        for (int q = 0; q < KMAX; ++q) {
+            if (PROG == 1 || q < k) {
+                Wide<T>::widen(x[q].w[w], y[q]);
+                if (PROG == 0 && (fold_mask & (1u << q))) {
+                    float f[L];
+                    Wide<T>::widen(xf[q].w[w], f);
+#pragma unroll
+                    for (int j = 0; j < L; ++j) y[q][j] = accf<O>(y[q][j], f[j]);
+                }
+            }
+        }
+        acc_steps<O, KMAX, L, PROG>(y, k, tree_mask, chain_mask);
+        x[0].w[w] = Wide<T>::narrow(y[0]);
+    }
+}
 
 }  // namespace mvx

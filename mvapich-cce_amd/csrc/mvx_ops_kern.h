@@ -3,7 +3,7 @@
 // path and what they take (Params, BodyParams), written for gfx950 (CDNA4,
 // wave64).  The ops on elements and chunks are in mvx_ops_fn.h; the host-side
 // tables that name every instantiation are in mvx_ops_tab.h, which mvx_ops.hip
-// and the per-op table units mvx_ops_{cmp,arith,logic,loc,half,fp8}.hip include.
+// and the per-op table units mvx_ops_{cmp,arith,logic,loc,half,fp8,acc32}.hip include.
 // Built into libmvx_hip.so; C-ABI in include/mvx_hip.h.
 //
 // One kernel template covers every predefined op x type of the reference
@@ -79,19 +79,46 @@ __device__ __forceinline__ void reduce_leaves(T (&y)[KMAX], int k, unsigned tree
     }
 }
 
+// the same element of every leaf through the f32-accumulating program
+// (acc_op): widened, folded and combined in f32, narrowed once.  A single
+// unfolded leaf has no step: it is copied, bits and all (a NaN's payload
+// would not survive the way to f32 and back), as the per-step ops copy it.
 template <int O, typename T, int KMAX>
-__device__ __forceinline__ void scalar_elem(const Params &P, long i)
+__device__ __forceinline__ void scalar_elem_acc(const Params &P, long i)
 {
-    T y[KMAX];
+    if (P.k == 1 && !P.fold[0]) {
+        store_elt(reinterpret_cast<T *>(P.dst) + i, reinterpret_cast<const T *>(P.src[0])[i]);
+        return;
+    }
+    float y[KMAX][1];
 #pragma unroll
     for (int q = 0; q < KMAX; ++q) {
         if (q < P.k) {
-            y[q] = reinterpret_cast<const T *>(P.src[q])[i];
-            if (P.fold[q]) y[q] = F<O, T>::f(y[q], reinterpret_cast<const T *>(P.fold[q])[i]);
+            y[q][0] = widen_elt(reinterpret_cast<const T *>(P.src[q]) + i);
+            if (P.fold[q]) y[q][0] = accf<O>(y[q][0], widen_elt(reinterpret_cast<const T *>(P.fold[q]) + i));
         }
     }
-    reduce_leaves<O, T, KMAX>(y, P.k, P.tree_mask, P.chain_mask);
-    store_elt(reinterpret_cast<T *>(P.dst) + i, y[0]);
+    acc_steps<O, KMAX, 1, 0>(y, P.k, P.tree_mask, P.chain_mask);
+    narrow_elt(reinterpret_cast<T *>(P.dst) + i, y[0][0]);
+}
+
+template <int O, typename T, int KMAX>
+__device__ __forceinline__ void scalar_elem(const Params &P, long i)
+{
+    if constexpr (acc_op<O>::v) {
+        scalar_elem_acc<O, T, KMAX>(P, i);
+    } else {
+        T y[KMAX];
+#pragma unroll
+        for (int q = 0; q < KMAX; ++q) {
+            if (q < P.k) {
+                y[q] = reinterpret_cast<const T *>(P.src[q])[i];
+                if (P.fold[q]) y[q] = F<O, T>::f(y[q], reinterpret_cast<const T *>(P.fold[q])[i]);
+            }
+        }
+        reduce_leaves<O, T, KMAX>(y, P.k, P.tree_mask, P.chain_mask);
+        store_elt(reinterpret_cast<T *>(P.dst) + i, y[0]);
+    }
 }
 
 // U = 16-byte chunks per lane per iteration (loads in flight per operand).
@@ -140,6 +167,33 @@ __device__ __forceinline__ void st_chunk(u32x4 *base, long c, const Chunk<T> &x)
     __builtin_memcpy(r, &x, sizeof x);
 #pragma unroll
     for (int w = 0; w < CG<T>::w; ++w) st<NT, alu_heavy<T>::v>(base + c * CG<T>::w + w, r[w]);
+}
+
+// The f32-accumulating ops' batch x[U][KMAX] of loaded chunks: the fold
+// partners' chunks are kept, and each chunk's program -- folds included -- is
+// evaluated in f32 (acc_chunk), the result left in x[u][0].
+template <int O, typename T, int KMAX, int U, int NT, int PROG>
+__device__ __forceinline__ void batch_acc(Chunk<T> (&x)[U][KMAX], const u32x4 *(&fold)[KMAX], long c0,
+                                          long nvec, int k, unsigned tree_mask, unsigned chain_mask)
+{
+    Chunk<T> xf[U][KMAX];
+    unsigned fmask = 0;
+    if constexpr (PROG == 0) {
+#pragma unroll
+        for (int q = 0; q < KMAX; ++q) {
+            if (q < k && fold[q]) {
+                fmask |= 1u << q;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const long c = c0 + (long)u * 256;
+                    if (c < nvec) xf[u][q] = ld_chunk<T, NT>(fold[q], c);
+                }
+            }
+        }
+    }
+    if (PROG == 0 && k == 1 && !fmask) return;     // a lone leaf is copied as it is (scalar_elem_acc)
+#pragma unroll
+    for (int u = 0; u < U; ++u) acc_chunk<O, T, KMAX, PROG>(x[u], xf[u], fmask, k, tree_mask, chain_mask);
 }
 
 // PROG = 0: the program comes from the masks (any chain of trees over
@@ -195,57 +249,61 @@ k_combine(const Params P)
                     if (PROG == 1 || q < k) x[u][q] = ld_chunk<T, NT>(src[q], c);
             }
         }
-#pragma unroll
-        for (int q = 0; q < KMAX; ++q) {
-            // fixed trees are launched without folded leaves (mvx_op_program):
-            // no branch between the loads and the tree keeps every load of
-            // the iteration in flight before the first add
-            if (PROG == 0 && q < k && fold[q]) {
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const long c = c0 + (long)u * 256;
-                    if (c < P.nvec) {
-                        const Chunk<T> f = ld_chunk<T, NT>(fold[q], c);
-                        CF<O, T>::f(x[u][q], f);
-                    }
-                }
-            }
-        }
-        // the combine program: each wave-uniform step is tested once and
-        // applied to all U*V elements of the batch (chunks past the end
-        // compute on unloaded registers and are never stored)
-        if constexpr (KMAX == 2) {
-            if (k == 2) {
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-                    CF<O, T>::f(x[u][0], x[u][1]);
-            }
-        } else if constexpr (PROG == 1) {
-#pragma unroll
-            for (int h = 1; h < KMAX; h <<= 1)
-#pragma unroll
-                for (int q = 0; q + h < KMAX; q += 2 * h)
-#pragma unroll
-                    for (int u = 0; u < U; ++u)
-                        CF<O, T>::f(x[u][q], x[u][q + h]);
+        if constexpr (acc_op<O>::v) {
+            batch_acc<O, T, KMAX, U, NT, PROG>(x, fold, c0, P.nvec, k, tmask, cmask);
         } else {
 #pragma unroll
-            for (int l = 0; (1 << l) < KMAX; ++l) {
+            for (int q = 0; q < KMAX; ++q) {
+                // fixed trees are launched without folded leaves (mvx_op_program):
+                // no branch between the loads and the tree keeps every load of
+                // the iteration in flight before the first add
+                if (PROG == 0 && q < k && fold[q]) {
 #pragma unroll
-                for (int q = 0; q + (1 << l) < KMAX; ++q) {
-                    if (tmask & (1u << (l * 8 + q))) {
-#pragma unroll
-                        for (int u = 0; u < U; ++u)
-                            CF<O, T>::f(x[u][q], x[u][q + (1 << l)]);
+                    for (int u = 0; u < U; ++u) {
+                        const long c = c0 + (long)u * 256;
+                        if (c < P.nvec) {
+                            const Chunk<T> f = ld_chunk<T, NT>(fold[q], c);
+                            CF<O, T>::f(x[u][q], f);
+                        }
                     }
                 }
             }
-#pragma unroll
-            for (int q = 1; q < KMAX; ++q) {
-                if (cmask & (1u << q)) {
+            // the combine program: each wave-uniform step is tested once and
+            // applied to all U*V elements of the batch (chunks past the end
+            // compute on unloaded registers and are never stored)
+            if constexpr (KMAX == 2) {
+                if (k == 2) {
 #pragma unroll
                     for (int u = 0; u < U; ++u)
-                        CF<O, T>::f(x[u][0], x[u][q]);
+                        CF<O, T>::f(x[u][0], x[u][1]);
+                }
+            } else if constexpr (PROG == 1) {
+#pragma unroll
+                for (int h = 1; h < KMAX; h <<= 1)
+#pragma unroll
+                    for (int q = 0; q + h < KMAX; q += 2 * h)
+#pragma unroll
+                        for (int u = 0; u < U; ++u)
+                            CF<O, T>::f(x[u][q], x[u][q + h]);
+            } else {
+#pragma unroll
+                for (int l = 0; (1 << l) < KMAX; ++l) {
+#pragma unroll
+                    for (int q = 0; q + (1 << l) < KMAX; ++q) {
+                        if (tmask & (1u << (l * 8 + q))) {
+#pragma unroll
+                            for (int u = 0; u < U; ++u)
+                                CF<O, T>::f(x[u][q], x[u][q + (1 << l)]);
+                        }
+                    }
+                }
+#pragma unroll
+                for (int q = 1; q < KMAX; ++q) {
+                    if (cmask & (1u << q)) {
+#pragma unroll
+                        for (int u = 0; u < U; ++u)
+                            CF<O, T>::f(x[u][0], x[u][q]);
+                    }
                 }
             }
         }
@@ -303,11 +361,15 @@ k_tree_body(const BodyParams P)
         for (int u = 0; u < U; ++u) {
             const long c = c0 + (long)u * 256;
             if (c < P.nvec) {
+                if constexpr (acc_op<O>::v) {
+                    acc_chunk<O, T, KMAX, 1>(x[u], x[u], 0u, KMAX, 0u, 0u);
+                } else {
 #pragma unroll
-                for (int h = 1; h < KMAX; h <<= 1)
+                    for (int h = 1; h < KMAX; h <<= 1)
 #pragma unroll
-                    for (int q = 0; q + h < KMAX; q += 2 * h)
-                        CF<O, T>::f(x[u][q], x[u][q + h]);
+                        for (int q = 0; q + h < KMAX; q += 2 * h)
+                            CF<O, T>::f(x[u][q], x[u][q + h]);
+                }
                 st_chunk<T, BODY_ST_NT>(P.dst, c, x[u][0]);
             }
         }
@@ -341,11 +403,94 @@ k_chain_body(const BodyParams P)
         for (int u = 0; u < U; ++u) {
             const long c = c0 + (long)u * 256;
             if (c < P.nvec) {
+                if constexpr (acc_op<O>::v) {
+                    acc_chunk<O, T, KMAX, 0>(x[u], x[u], 0u, k, 0u, (1u << k) - 2u);
+                } else {
 #pragma unroll
-                for (int q = 1; q < KMAX; ++q)
-                    if (q < k) CF<O, T>::f(x[u][0], x[u][q]);
+                    for (int q = 1; q < KMAX; ++q)
+                        if (q < k) CF<O, T>::f(x[u][0], x[u][q]);
+                }
                 st_chunk<T, BODY_ST_NT>(P.dst, c, x[u][0]);
             }
+        }
+    }
+}
+
+// The masked program of an f32-accumulating op with one side in f32: what a
+// program over more than 8 leaves is cut into (mvx_combine.c), its
+// intermediates being f32 temporaries.  DIR = 0: narrow leaves (folds
+// allowed), f32 result, not narrowed; DIR = 1: f32 leaves, the result narrowed
+// once.  A lane takes one 32-bit word of each narrow operand against L floats
+// of each f32 one (a dwordx4 for the 8-bit types, a dwordx2 for the 16-bit
+// ones).  Params: head elements lead to nvec such words where the narrow
+// side is 4-byte and the f32 side 4 * L-byte aligned (vec_ok), else every
+// element goes alone.
+template <typename T, int DIR>
+__device__ __forceinline__ float ld_f32side(const char *p, long i)
+{
+    if constexpr (DIR == 0) return widen_elt(reinterpret_cast<const T *>(p) + i);
+    else return reinterpret_cast<const float *>(p)[i];
+}
+
+template <int O, typename T, int DIR>
+__global__ void __launch_bounds__(256)
+k_combine_f32(const Params P)
+{
+    constexpr int L = Wide<T>::L;
+    constexpr int KMAX = MVX_COMBINE_KMAX;
+    typedef float fL __attribute__((ext_vector_type(L)));
+    const long tid = (long)blockIdx.x * 256 + threadIdx.x;
+    const long nthr = (long)gridDim.x * 256;
+    const int k = P.k;
+    const unsigned tmask = P.tree_mask, cmask = P.chain_mask;
+    {   // every element (operands misaligned), or the head and the tail
+        const long tail0 = P.vec_ok ? P.head + P.nvec * L : 0;
+        const long nscal = P.vec_ok ? P.head + (P.n - tail0) : P.n;
+        for (long s = tid; s < nscal; s += nthr) {
+            const long i = !P.vec_ok || s < P.head ? s : tail0 + (s - P.head);
+            float y[KMAX][1];
+#pragma unroll
+            for (int q = 0; q < KMAX; ++q) {
+                if (q < k) {
+                    y[q][0] = ld_f32side<T, DIR>(P.src[q], i);
+                    if (DIR == 0 && P.fold[q]) y[q][0] = accf<O>(y[q][0], ld_f32side<T, 0>(P.fold[q], i));
+                }
+            }
+            acc_steps<O, KMAX, 1, 0>(y, k, tmask, cmask);
+            if constexpr (DIR == 0) reinterpret_cast<float *>(P.dst)[i] = y[0][0];
+            else narrow_elt(reinterpret_cast<T *>(P.dst) + i, y[0][0]);
+        }
+        if (!P.vec_ok) return;
+    }
+    const long nb = P.head * (long)sizeof(T), fb = P.head * 4;   // the body's byte offset on either side
+    for (long c = tid; c < P.nvec; c += nthr) {
+        float y[KMAX][L];
+#pragma unroll
+        for (int q = 0; q < KMAX; ++q) {
+            if (q < k) {
+                if constexpr (DIR == 0) {
+                    Wide<T>::widen(reinterpret_cast<const uint32_t *>(P.src[q] + nb)[c], y[q]);
+                    if (P.fold[q]) {
+                        float f[L];
+                        Wide<T>::widen(reinterpret_cast<const uint32_t *>(P.fold[q] + nb)[c], f);
+#pragma unroll
+                        for (int j = 0; j < L; ++j) y[q][j] = accf<O>(y[q][j], f[j]);
+                    }
+                } else {
+                    const fL v = reinterpret_cast<const fL *>(P.src[q] + fb)[c];
+#pragma unroll
+                    for (int j = 0; j < L; ++j) y[q][j] = v[j];
+                }
+            }
+        }
+        acc_steps<O, KMAX, L, 0>(y, k, tmask, cmask);
+        if constexpr (DIR == 0) {
+            fL v;
+#pragma unroll
+            for (int j = 0; j < L; ++j) v[j] = y[0][j];
+            reinterpret_cast<fL *>(P.dst + fb)[c] = v;
+        } else {
+            reinterpret_cast<uint32_t *>(P.dst + nb)[c] = Wide<T>::narrow(y[0]);
         }
     }
 }

@@ -3,7 +3,7 @@
 // (Config), the descriptor of one kernel instantiation (KVar), the families
 // and sets built from them, the element kinds and the per-op table units'
 // lookup functions.  Included by mvx_ops.hip (dispatch and launch policy) and
-// by mvx_ops_{cmp,arith,logic,loc,half,fp8}.hip, which instantiate the kernels of
+// by mvx_ops_{cmp,arith,logic,loc,half,fp8,acc32}.hip, which instantiate the kernels of
 // mvx_ops_kern.h through the macros below, one translation unit each so that
 // they compile in parallel.
 #include <stdio.h>
@@ -58,7 +58,8 @@ typedef const char *(*SymFn)();
 // template arguments, so profiles and PMC summaries can be matched to what
 // actually ran.
 inline constexpr char K_COMBINE[] = "k_combine", K_TREE_BODY[] = "k_tree_body",
-                      K_CHAIN_BODY[] = "k_chain_body", K_PXI_LOC_BODY[] = "k_pxi_loc_body";
+                      K_CHAIN_BODY[] = "k_chain_body", K_PXI_LOC_BODY[] = "k_pxi_loc_body",
+                      K_COMBINE_F32[] = "k_combine_f32";
 
 template <const char *BASE, int O, typename T, int... A>
 static const char *ksym()
@@ -106,6 +107,7 @@ struct KSet {
     KFam prog4;            // programs over 3 or 4 leaves: KMAX 4 at U = 2 (MVX_PROG4=0: prog)
     KFam tree8, tree4;     // PROG = 1: full trees over 8 / 4 leaves
     KFam chain8, chain4;   // full chains over 8 / 4 leaves: k_chain_body, else the masked program
+    KVar f32side[2];       // the f32-accumulating ops: k_combine_f32, f32 result [0] / f32 leaves [1]; else empty
     int esize;
     int chunk;             // bytes per chunk (16, or the element if wider)
     const char *name;
@@ -203,6 +205,11 @@ static KSet kset(const char *name)
     } else {
         s.prog2 = {};
     }
+    s.f32side[0] = s.f32side[1] = KVar{};
+    if constexpr (acc_op<O>::v) {
+        s.f32side[0] = {(const void *)&k_combine_f32<O, T, 0>, &ksym<K_COMBINE_F32, O, T, 0>, 1, false, 1, 0, 1, MVX_COMBINE_KMAX};
+        s.f32side[1] = {(const void *)&k_combine_f32<O, T, 1>, &ksym<K_COMBINE_F32, O, T, 1>, 1, false, 1, 0, 1, MVX_COMBINE_KMAX};
+    }
     s.esize = (int)sizeof(T);
     s.chunk = CG<T>::bytes;
     s.name = name;
@@ -278,5 +285,6 @@ int flog_sync();                            // MPI_LOGICAL's words on this devic
 const KSet *lookup_loc(int op, int ek);     // MAXLOC, MINLOC     mvx_ops_loc.hip
 const KSet *lookup_half(int op, int ek);    // every op on the 16-bit floats  mvx_ops_half.hip
 const KSet *lookup_fp8(int op, int ek);     // every op on the 8-bit floats   mvx_ops_fp8.hip
+const KSet *lookup_acc32(int op, int ek);   // MVX_SUM_ACC32, MVX_PROD_ACC32  mvx_ops_acc32.hip
 
 }  // namespace mvx

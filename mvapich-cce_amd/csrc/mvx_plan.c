@@ -183,6 +183,7 @@ static int op_symmetric(int op, int dtype)
     switch (op) {
     case MPI_SUM: case MPI_PROD: case MPI_LAND: case MPI_LOR: case MPI_LXOR:
     case MPI_BAND: case MPI_BOR: case MPI_BXOR:
+    case MVX_SUM_ACC32: case MVX_PROD_ACC32:   /* f32 add and multiply commute */
         return 1;
     case MPI_MAX: case MPI_MIN:
         return !is_ieee(dtype);

@@ -16,7 +16,8 @@ the launch stream), GB/s and fraction of the 8 TB/s HBM peak.
 
 Modes (arguments): sweep, all, all-tree, ks, x87 add lines to the four
 configs; half runs only the 16-bit floating types against MPI_SHORT, fp8 only
-the 8-bit ones against MPI_UNSIGNED_CHAR.
+the 8-bit ones against MPI_UNSIGNED_CHAR, acc32 only MVX_SUM_ACC32 /
+MVX_PROD_ACC32 against MPI_SUM / MPI_PROD on the four narrow floating types.
 """
 import importlib
 import json
@@ -117,8 +118,30 @@ def fp8(mvx):
             run(mvx, "F8-%s-%s" % (on, tn), op, t, 8, 0, 32 * MIB, 4, reps=10, warm=2)
 
 
+NARROW = ((72, "e4m3"), (73, "e5m2"), (64, "f16"), (65, "bf16"))
+
+
+def acc32(mvx):
+    """The f32-accumulating ops next to the per-step op on the same type, pair
+    by pair (wide, then narrow): the apply kernel at 256 MiB vectors, the
+    8-leaf tree at 32 MiB leaves and the 4-leaf chain at 256 MiB leaves (the
+    C2 / C3 / C4 shapes).  Both move the same bytes; the wide form converts
+    less and keeps more registers."""
+    for wide, step, on in ((mvx.MVX_SUM_ACC32, mvx.MPI_SUM, "sum"), (mvx.MVX_PROD_ACC32, mvx.MPI_PROD, "prod")):
+        for t, tn in NARROW:
+            for op, kind in ((wide, "acc32"), (step, "step")):
+                run(mvx, "W2-%s-%s-%s" % (on, tn, kind), op, t, 2, 1, 256 * MIB, 4, reps=10, warm=2)
+            for op, kind in ((wide, "acc32"), (step, "step")):
+                run(mvx, "W8-%s-%s-%s" % (on, tn, kind), op, t, 8, 0, 32 * MIB, 4, reps=10, warm=2)
+            for op, kind in ((wide, "acc32"), (step, "step")):
+                run(mvx, "W4-%s-%s-%s" % (on, tn, kind), op, t, 4, 1, 256 * MIB, 2, reps=10, warm=2)
+
+
 def main():
     mvx = importlib.import_module("mvapich-cce_amd")
+    if "acc32" in sys.argv[1:]:
+        acc32(mvx)
+        return
     if "fp8" in sys.argv[1:]:
         fp8(mvx)
         return
@@ -150,6 +173,9 @@ def main():
                 if hip.mvx_op_supported(op, t) != 1:
                     continue
                 run(mvx, "A-%d-%d" % (op, t), op, t, 2, 1, 256 * MIB, 4, reps=10, warm=2)
+        for op in (mvx.MVX_SUM_ACC32, mvx.MVX_PROD_ACC32):      # the extension ops: their four types
+            for t, _ in NARROW:
+                run(mvx, "A-%d-%d" % (op, t), op, t, 2, 1, 256 * MIB, 4, reps=10, warm=2)
     if "all-tree" in sys.argv[1:]:
         # the same pairs as 8-leaf trees over 32 MiB leaves (the C3 shape)
         hip = mvx.hip()
@@ -159,6 +185,9 @@ def main():
             for t in types:
                 if hip.mvx_op_supported(op, t) != 1:
                     continue
+                run(mvx, "T-%d-%d" % (op, t), op, t, 8, 0, 32 * MIB, 4, reps=10, warm=2)
+        for op in (mvx.MVX_SUM_ACC32, mvx.MVX_PROD_ACC32):
+            for t, _ in NARROW:
                 run(mvx, "T-%d-%d" % (op, t), op, t, 8, 0, 32 * MIB, 4, reps=10, warm=2)
     if "ks" in sys.argv[1:]:
         # every leaf count 2..8, tree and chain (the masked program where no
