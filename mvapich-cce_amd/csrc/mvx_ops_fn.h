@@ -137,6 +137,33 @@ template <typename T> struct F<OMAXLOC, T> {
 template <typename T> struct F<OMINLOC, T> {
     static __device__ __forceinline__ T f(T a, T b) { return loc_op<T, true>(a, b); }
 };
+// contiguous(2, MPI_CHAR): the same op on 32-bit values.  On int8_t members
+// the compiler chained the steps of a program as byte-select (SDWA)
+// instructions and compared a sign-extended byte -- the value a previous step
+// had selected -- with a zero-extended one (v_cmp_eq_u16_sdwa sext(x), y):
+// equal negative values compared unequal and the loc = min rule was skipped
+// from the second step on (element path of the 3- and 4-leaf programs;
+// tests/test_gpu_kernel_matrix.py).  The empty asm makes the four widened
+// values opaque, so every compare and select is a 32-bit one.
+template <bool MIN>
+__device__ __forceinline__ pp<int8_t> loc_op8(pp<int8_t> a, pp<int8_t> b)
+{
+    int av = a.v, al = a.l, bv = b.v, bl = b.l;
+    __asm__("" : "+v"(av), "+v"(al), "+v"(bv), "+v"(bl));
+    const bool eq = av == bv;
+    const bool take = MIN ? (av > bv) : (av < bv);
+    const int lmin = (al > bl) ? bl : al;
+    pp<int8_t> r;
+    r.v = (int8_t)(take ? bv : av);
+    r.l = (int8_t)(eq ? lmin : (take ? bl : al));
+    return r;
+}
+template <> struct F<OMAXLOC, pp<int8_t>> {
+    static __device__ __forceinline__ pp<int8_t> f(pp<int8_t> a, pp<int8_t> b) { return loc_op8<false>(a, b); }
+};
+template <> struct F<OMINLOC, pp<int8_t>> {
+    static __device__ __forceinline__ pp<int8_t> f(pp<int8_t> a, pp<int8_t> b) { return loc_op8<true>(a, b); }
+};
 
 // the x87 types (global_ops.c:149-155 and the HAVE_LONG_DOUBLE case of every
 // op; 1365-1378 / 1605-1618 for LONG_DOUBLE_INT)

@@ -123,13 +123,17 @@ def _ran_as_planned(mvx, planned, what):
     return ran[:2]
 
 
-def combine(mvx, op, dtype, k, shape, n, offset=0, folded=False, seed=0, ties=0.0, misalign=False):
+def combine(mvx, op, dtype, k, shape, n, offset=0, folded=False, seed=0, ties=0.0, misalign=False, data=None):
     """op_combine over k leaves of n elements, every operand `offset` bytes
     off the 16-byte grid (misalign: each at an offset of its own, so the
-    kernel's vec_ok is 0).  Returns (kernel symbol, grid blocks)."""
+    kernel's vec_ok is 0).  data: (leaves, fold partners) to use in place of
+    leaves()'s -- k arrays of n elements, and k arrays or None, None wherever
+    `folded` has no partner.  Returns (kernel symbol, grid blocks)."""
     import torch
     E = mvx.dtype_info(dtype)[0]
-    S, F = leaves(dtype, k, n, seed, ties, folded)
+    S, F = leaves(dtype, k, n, seed, ties, folded) if data is None else data
+    assert len(S) == len(F) == k and all(len(x) == n and x.dtype == S[0].dtype for x in S), (k, n)
+    assert [x is not None for x in F] == [bool(folded and q % 2) for q in range(k)], "fold partners: the odd leaves"
     npd = S[0].dtype
     so, fo, do = _offsets(E, k, offset, folded, misalign)
     dS = [_place(x, so[q], q)[1] for q, x in enumerate(S)]
@@ -145,12 +149,14 @@ def combine(mvx, op, dtype, k, shape, n, offset=0, folded=False, seed=0, ties=0.
     return sym, blocks
 
 
-def apply(mvx, oracle, op, dtype, n, offset=0, seed=0, ties=0.0, misalign=False):
-    """The plain op in place (mvx_op_apply: inout = in op inout).  Returns
-    (kernel symbol, grid blocks)."""
+def apply(mvx, oracle, op, dtype, n, offset=0, seed=0, ties=0.0, misalign=False, data=None):
+    """The plain op in place (mvx_op_apply: inout = in op inout).  data: (in,
+    inout) of n elements to use in place of leaves()'s.  Returns (kernel
+    symbol, grid blocks)."""
     import torch
     E = mvx.dtype_info(dtype)[0]
-    (a, b), _ = leaves(dtype, 2, n, seed, 0.0)
+    (a, b), _ = leaves(dtype, 2, n, seed, 0.0) if data is None else (data, None)
+    assert len(a) == len(b) == n and a.dtype == b.dtype, (n, len(a), len(b))
     if ties:
         sel = np.random.default_rng(seed).random(n) < ties
         a.view(np.uint8).reshape(n, -1)[sel, :10] = b.view(np.uint8).reshape(n, -1)[sel, :10]
@@ -188,16 +194,16 @@ def _planned(got):
     return got[:2]
 
 
-def plan_combine(mvx, op, dtype, k, shape, n, offset=0, folded=False, seed=0, ties=0.0, misalign=False):
+def plan_combine(mvx, op, dtype, k, shape, n, offset=0, folded=False, seed=0, ties=0.0, misalign=False, data=None):
     """What `combine` with these arguments would launch: (kernel symbol, grid
-    blocks) from mvx_op_plan; seed and ties (the data) play no part."""
+    blocks) from mvx_op_plan; seed, ties and data (the data) play no part."""
     so, fo, do = _offsets(mvx.dtype_info(dtype)[0], k, offset, folded, misalign)
     srcs = [_fake(q, o) for q, o in enumerate(so)]
     folds = [_fake(20 + q, o) if o is not None else None for q, o in enumerate(fo)] if folded else None
     return _planned(_plan(mvx, op, dtype, srcs, folds, _fake(40, do), n, shape))
 
 
-def plan_apply(mvx, oracle, op, dtype, n, offset=0, seed=0, ties=0.0, misalign=False):
+def plan_apply(mvx, oracle, op, dtype, n, offset=0, seed=0, ties=0.0, misalign=False, data=None):
     """What `apply` with these arguments would launch (oracle is not used)."""
     da = _fake(1, _offsets(mvx.dtype_info(dtype)[0], 1, offset, False, misalign)[0][0])
     db = _fake(2, offset)
