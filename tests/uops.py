@@ -20,6 +20,11 @@ UOPS = {
     "affine": (9, 0, np.uint64),
 }
 
+# ops on struct {int a; (4-byte hole); double b}, a derived type the tests
+# build themselves (extent 16, size 12): name -> associative and commutative?
+IDPAIR_UOPS = {"idsum": True, "idmix": False}
+IDPAIR_EXTENT = 16
+
 _host = None
 _dev = None
 
@@ -62,6 +67,20 @@ def dev_lib():
 
 def dev_fn(name):
     return ctypes.cast(getattr(dev_lib(), "duop_" + name), ctypes.c_void_p).value
+
+
+def rand_idpair(n, seed):
+    """n elements of struct {int a; hole; double b} as bytes at the type's
+    extent (IDPAIR_UOPS' operands): a anywhere in the int range, b finite
+    with exponents spread so that a sum or difference rounds, random bytes in
+    the hole."""
+    rng = np.random.default_rng(seed)
+    v = rng.integers(0, 256, (n, IDPAIR_EXTENT), dtype=np.uint8)
+    a = rng.integers(-(1 << 31), 1 << 31, n).astype(np.int32)
+    b = (rng.standard_normal(n) * 10.0 ** rng.integers(-3, 4, n)).astype(np.float64)
+    v[:, 0:4] = a.view(np.uint8).reshape(n, 4)
+    v[:, 8:16] = b.view(np.uint8).reshape(n, 8)
+    return v.reshape(-1)
 
 
 def rand_for(name, n, seed):

@@ -17,6 +17,10 @@
  *   uop_idsum   struct {int a; (4-byte hole); double b}, a derived struct
  *                        type: a and b summed field by field, the hole
  *                        never read or written
+ *   uop_idmix   the same struct: a mixed as uop_mix mixes its words, b = in.b -
+ *                        inout.b -- neither commutative nor associative in
+ *                        either field, one floating operation per field (so
+ *                        nothing can be contracted), the hole never touched
  */
 #include <stdint.h>
 
@@ -100,5 +104,17 @@ void uop_idsum(void *in, void *inout, int *len, int *dt)
     for (int i = 0; i < *len; i++) {
         y[i].a = (int)((unsigned)x[i].a + (unsigned)y[i].a);
         y[i].b = x[i].b + y[i].b;
+    }
+}
+
+void uop_idmix(void *in, void *inout, int *len, int *dt)
+{
+    const idpair_t *x = (const idpair_t *)in;
+    idpair_t *y = (idpair_t *)inout;
+    (void)dt;
+    for (int i = 0; i < *len; i++) {
+        const unsigned ya = (unsigned)y[i].a;
+        y[i].a = (int)((unsigned)x[i].a * 31u + (ya ^ (ya >> 3)) * 7u + 1u);
+        y[i].b = x[i].b - y[i].b;
     }
 }

@@ -58,18 +58,30 @@ __global__ void __launch_bounds__(256) k_idsum(const IdPair *x, IdPair *y, size_
     }
 }
 
-}  // namespace
-
-extern "C" int duop_idsum(const void *in, void *inout, size_t len, int dt, void *s)
+// uop_idmix: one floating operation per field, the hole never touched
+__global__ void __launch_bounds__(256) k_idmix(const IdPair *x, IdPair *y, size_t n)
 {
-    (void)dt;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const unsigned ya = (unsigned)y[i].a;
+        y[i].a = (int)((unsigned)x[i].a * 31u + (ya ^ (ya >> 3)) * 7u + 1u);
+        y[i].b = x[i].b - y[i].b;
+    }
+}
+
+int launch_idpair(void (*k)(const IdPair *, IdPair *, size_t), const void *in, void *inout, size_t len, void *s)
+{
     if (len == 0) return 0;
     size_t blocks = (len + 255) / 256;
     if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(k_idsum, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)s, (const IdPair *)in,
+    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)s, (const IdPair *)in,
                        (IdPair *)inout, len);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
+
+}  // namespace
+
+extern "C" int duop_idsum(const void *in, void *inout, size_t len, int dt, void *s) { (void)dt; return launch_idpair(k_idsum, in, inout, len, s); }
+extern "C" int duop_idmix(const void *in, void *inout, size_t len, int dt, void *s) { (void)dt; return launch_idpair(k_idmix, in, inout, len, s); }
 
 extern "C" int duop_mix(const void *in, void *inout, size_t len, int dt, void *s) { (void)dt; return launch<Mix>(in, inout, len, s); }
 extern "C" int duop_affine(const void *in, void *inout, size_t len, int dt, void *s) { (void)dt; return launch<Affine>(in, inout, len, s); }
