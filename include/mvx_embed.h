@@ -43,6 +43,10 @@ extern "C" {
 #define MVX_SUM_ACC32         164   /* SUM, accumulated in f32, one rounding */
 #define MVX_PROD_ACC32        165   /* PROD, accumulated in f32, one rounding */
 #endif
+/* and the ranks' mean, on those four and on the f32 / f64 types (mvx_mpi.h) */
+#ifndef MVX_AVG
+#define MVX_AVG               168
+#endif
 
 /* communicators: one process per GPU, collective over `size` processes.
  * Creation and every call on a communicator run on its device and leave the

@@ -48,7 +48,8 @@ extern "C" {
  * reference handle, a derived one, or one of the extension types
  * MVX_FLOAT16 / MVX_BFLOAT16 / MVX_FLOAT8_E4M3 / MVX_FLOAT8_E5M2 (mvx_mpi.h),
  * which have MPI_FLOAT's seven ops and, alone, the two extension ops
- * MVX_SUM_ACC32 / MVX_PROD_ACC32. */
+ * MVX_SUM_ACC32 / MVX_PROD_ACC32; MVX_AVG has those four and the f32 / f64
+ * types. */
 int mvx_op_supported(int op, int dtype);
 /* Bytes of one element as the (op, dtype) kernel reads it (the C pair
  * struct for MAXLOC / MINLOC on a struct type), or 0 if undefined. */
@@ -181,6 +182,22 @@ int mvx_op_program_f32(int op, int dtype, const void *const *srcs,
                        const void *const *fold, int k, unsigned tree_mask,
                        unsigned chain_mask, void *dst, size_t n, int side,
                        void *hip_stream);
+
+/* MVX_AVG (mvx_mpi.h) through the entry points above divides by the leaves it
+ * is given, k plus the non-null fold partners: mvx_op_apply is
+ * (in + inout) / 2.  This form takes the divisor (>= 1) instead -- the last
+ * launch of a program over more than MVX_COMBINE_KMAX leaves, whose earlier
+ * launches are sums (MPI_SUM on MPI_FLOAT / MPI_DOUBLE, MVX_SUM_ACC32 with
+ * MVX_F32_OUT on the narrow types).
+ *   side 0         : leaves and dst of dtype, as mvx_op_program.
+ *   side MVX_F32_IN: narrow dtypes only; leaves n floats each (4-byte aligned,
+ *                    no fold partners), the f32 value divided, then narrowed
+ *                    once.
+ * Return codes of mvx_op_program; MPI_ERR_ARG for a divisor below 1, another
+ * side, MVX_F32_IN on MPI_FLOAT / MPI_DOUBLE, or a misaligned f32 leaf. */
+int mvx_op_program_avg(int dtype, const void *const *srcs, const void *const *fold,
+                       int k, unsigned tree_mask, unsigned chain_mask, void *dst,
+                       size_t n, int side, int divisor, void *hip_stream);
 
 /* What mvx_op_program would launch for these arguments, without launching:
  * the same checks and return codes, then the kernel template as rocprofv3

@@ -122,6 +122,20 @@ typedef long MPI_Aint;      /* x86-64 LP64, the reference build's address int */
 #define MVX_SUM_ACC32         164   /* SUM, accumulated in f32, one rounding */
 #define MVX_PROD_ACC32        165   /* PROD, accumulated in f32, one rounding */
 #endif
+/* EXTENSION: the ranks' mean (RCCL's ncclAvg), what a gradient reduction asks
+ * for.  MPI_SUM's result for the same call -- the plan's order and roles, bit
+ * for bit -- divided ONCE by the number of rank contributions the rank's
+ * combine program consumed: p for Allreduce, Reduce_scatter and Reduce's
+ * root, rank + 1 for Scan.  Defined on MPI_FLOAT / MPI_REAL and MPI_DOUBLE /
+ * MPI_DOUBLE_PRECISION (one correctly rounded IEEE division in the type) and
+ * on the four narrow floating types, where the sum is MVX_SUM_ACC32's binary32
+ * value, divided in binary32 and narrowed once: eight ranks' 448 in E4M3 give
+ * 448, where either sum gives NaN.  A lone contribution (p = 1, Scan's rank
+ * 0) is copied.  Every other (op, type) pair answers 329 (DESIGN.md section
+ * 7).  Also defined, with the same value, in mvx_embed.h. */
+#ifndef MVX_AVG
+#define MVX_AVG               168
+#endif
 
 /* Ops: reference include/mpi.h:127-140 */
 #define MPI_OP_NULL ((MPI_Op)0)

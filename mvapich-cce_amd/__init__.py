@@ -128,6 +128,7 @@ def _load():
     _hip.mvx_op_program.argtypes = [i, i, pvp, pvp, i, ctypes.c_uint, ctypes.c_uint, vp, sz, vp]
     _hip.mvx_op_plan.argtypes = [i, i, pvp, pvp, i, ctypes.c_uint, ctypes.c_uint, vp, sz, vp]
     _hip.mvx_op_program_f32.argtypes = [i, i, pvp, pvp, i, ctypes.c_uint, ctypes.c_uint, vp, sz, i, vp]
+    _hip.mvx_op_program_avg.argtypes = [i, pvp, pvp, i, ctypes.c_uint, ctypes.c_uint, vp, sz, i, i, vp]
     _hip.mvx_tree_mask.argtypes = [i]
     _hip.mvx_tree_mask.restype = ctypes.c_uint
     _hip.mvx_chain_mask.argtypes = [i]

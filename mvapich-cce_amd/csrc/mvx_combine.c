@@ -3,7 +3,8 @@
  * reference's order.  Predefined ops on <= 8 leaves are one kernel launch
  * (mvx_op_program, libmvx_hip.so); wider programs run as groups of 8 with the
  * same association (the f32-accumulating extension ops through f32
- * temporaries, so nothing is narrowed before the end); user functions get
+ * temporaries, so nothing is narrowed before the end; MVX_AVG as its sum,
+ * divided in the last launch); user functions get
  * the reference's operand roles (host MPI_User_functions through pinned
  * scratch, device functions in HBM); datatypes with holes are unpacked to the extent layout the op sees.
  * Reference: the (*uop) calls of intra_fns_new.c (e.g. 5505-5512, 5681-5699)
@@ -133,40 +134,61 @@ static char *scratch_take(scratch_t *S)
  * a temporary of its own by a 1-leaf launch.  mvxi_wide_temps has the slot
  * for it: a raw leaf reaches a later round only as the single trailing leaf
  * of a tree's first round or as a one-leaf segment among the chain's heads,
- * and either is counted there as a group or a segment that takes none. */
+ * and either is counted there as a group or a segment that takes none.
+ *
+ * MVX_AVG is its sum until the program's last launch: MPI_SUM on the type
+ * itself for float and double, MVX_SUM_ACC32 with the f32 temporaries above
+ * for the narrow floats, so the temporaries, their slots and every launch
+ * but the last are that op's.  The last launch (DST_LAST) divides by the
+ * whole program's rank contributions, which a launch's own leaves no longer
+ * tell: mvx_op_program_avg takes them as an argument. */
+#define DST_WIDE 1   /* dst takes the f32 value (a temporary of an f32-accumulating program) */
+#define DST_LAST 2   /* dst is the program's result */
+
+static int avg_divisor(const mvx_plan *P)
+{
+    int q, d = P->k;
+    for (q = 0; q < P->k; q++) d += P->leaf_fold[q] >= 0;
+    return d;
+}
+
 static int launch_prog(const mvx_plan *P, leafref *v, int m, unsigned tmask,
-                       unsigned cmask, void *dst, int dst_wide, scratch_t *S, hipStream_t st)
+                       unsigned cmask, void *dst, int dflags, scratch_t *S, hipStream_t st)
 {
     const void *srcs[MVX_COMBINE_KMAX], *fold[MVX_COMBINE_KMAX];
     const size_t n = (size_t)P->c_cnt;
+    const int dst_wide = dflags & DST_WIDE, avg = mvxi_avg(P->op);
+    const int op = !avg ? P->op : mvxi_wide_f32(P) ? MVX_SUM_ACC32 : MPI_SUM;   /* every launch but AVG's last */
     int q, nw = 0, rc;
     if (!dst) return MPI_ERR_INTERN;
     for (q = 0; q < m; q++) nw += v[q].wide;
     if (nw || dst_wide) {
-        if (!mvxi_acc32(P->op)) return MPI_ERR_INTERN;
+        if (!mvxi_wide_f32(P)) return MPI_ERR_INTERN;
         for (q = 0; nw && q < m; q++) {
             char *t;
             if (v[q].wide) continue;
             if (!(t = scratch_take(S))) return MPI_ERR_INTERN;
-            if (S->base && (rc = mvx_op_program_f32(P->op, P->dtype, &v[q].p, &v[q].f, 1, 0u, 0u, t, n, MVX_F32_OUT, st)))
+            if (S->base && (rc = mvx_op_program_f32(op, P->dtype, &v[q].p, &v[q].f, 1, 0u, 0u, t, n, MVX_F32_OUT, st)))
                 return rc;
             v[q].p = t; v[q].f = NULL; v[q].wide = 1;
         }
     }
     for (q = 0; q < m; q++) { srcs[q] = v[q].p; fold[q] = v[q].f; }
     if (!S->base) return MPI_SUCCESS;
-    if (!nw && !dst_wide) return mvx_op_program(P->op, P->dtype, srcs, fold, m, tmask, cmask, dst, n, st);
-    if (!nw) return mvx_op_program_f32(P->op, P->dtype, srcs, fold, m, tmask, cmask, dst, n, MVX_F32_OUT, st);
-    if (!dst_wide) return mvx_op_program_f32(P->op, P->dtype, srcs, NULL, m, tmask, cmask, dst, n, MVX_F32_IN, st);
-    return mvx_op_program(P->op == MVX_SUM_ACC32 ? MPI_SUM : MPI_PROD, MPI_FLOAT, srcs, NULL, m, tmask, cmask, dst,
-                          n, st);
+    if (avg && (dflags & DST_LAST))
+        return mvx_op_program_avg(P->dtype, srcs, nw ? NULL : fold, m, tmask, cmask, dst, n, nw ? MVX_F32_IN : 0,
+                                  avg_divisor(P), st);
+    if (!nw && !dst_wide) return mvx_op_program(op, P->dtype, srcs, fold, m, tmask, cmask, dst, n, st);
+    if (!nw) return mvx_op_program_f32(op, P->dtype, srcs, fold, m, tmask, cmask, dst, n, MVX_F32_OUT, st);
+    if (!dst_wide) return mvx_op_program_f32(op, P->dtype, srcs, NULL, m, tmask, cmask, dst, n, MVX_F32_IN, st);
+    return mvx_op_program(op == MVX_SUM_ACC32 ? MPI_SUM : MPI_PROD, MPI_FLOAT, srcs, NULL, m, tmask, cmask, dst, n, st);
 }
 
-/* dst_wide: dst takes the f32 value (a temporary of an f32-accumulating op) */
-static int tree_eval(const mvx_plan *P, leafref *v, int m, void *dst, int dst_wide, scratch_t *S,
+/* dflags: what dst is (DST_*) */
+static int tree_eval(const mvx_plan *P, leafref *v, int m, void *dst, int dflags, scratch_t *S,
                      hipStream_t st)
 {
-    const int acc = mvxi_acc32(P->op);
+    const int acc = mvxi_wide_f32(P);
     int rc;
     while (m > MVX_COMBINE_KMAX) {
         const int ng = (m + 7) / 8;
@@ -181,12 +203,12 @@ static int tree_eval(const mvx_plan *P, leafref *v, int m, void *dst, int dst_wi
         }
         m = ng;
     }
-    return launch_prog(P, v, m, mvx_tree_mask(m), 0u, dst, dst_wide, S, st);
+    return launch_prog(P, v, m, mvx_tree_mask(m), 0u, dst, dflags, S, st);
 }
 
 static int chain_eval(const mvx_plan *P, leafref *v, int m, void *dst, scratch_t *S, hipStream_t st)
 {
-    const int acc = mvxi_acc32(P->op);
+    const int acc = mvxi_wide_f32(P);
     int i = 0, rc;
     while (m - i > MVX_COMBINE_KMAX) {
         char *t = scratch_take(S);
@@ -194,7 +216,7 @@ static int chain_eval(const mvx_plan *P, leafref *v, int m, void *dst, scratch_t
         i += 7;
         v[i].p = t; v[i].f = NULL; v[i].wide = acc;
     }
-    return launch_prog(P, v + i, m - i, 0u, mvx_chain_mask(m - i), dst, 0, S, st);
+    return launch_prog(P, v + i, m - i, 0u, mvx_chain_mask(m - i), dst, DST_LAST, S, st);
 }
 
 /* scratch slots a >8-leaf program can take: per segment its group temps
@@ -217,13 +239,13 @@ static int combine_wide(const mvx_plan *P, const void *const *srcs, const void *
     leafref v[MVX_MAXK], heads[MVX_MAXK];
     int q, s, e, nh = 0, rc;
     for (q = 0; q < P->k; q++) { v[q].p = srcs[q]; v[q].f = fold[q]; v[q].wide = 0; }
-    if (seg_end(P, 0) == P->k) return tree_eval(P, v, P->k, dst, 0, S, st);
+    if (seg_end(P, 0) == P->k) return tree_eval(P, v, P->k, dst, DST_LAST, S, st);
     for (s = 0; s < P->k; s = e) {
         e = seg_end(P, s);
         if (e - s == 1) { heads[nh++] = v[s]; continue; }
         heads[nh].p = scratch_take(S);
         heads[nh].f = NULL;
-        heads[nh].wide = mvxi_acc32(P->op);
+        heads[nh].wide = mvxi_wide_f32(P);
         if ((rc = tree_eval(P, v + s, e - s, (void *)heads[nh].p, heads[nh].wide, S, st))) return rc;
         nh++;
     }

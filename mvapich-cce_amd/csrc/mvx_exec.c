@@ -458,7 +458,7 @@ static int run_device_coll(mvx_comm_t *c, const job_t *J, long b, hipStream_t st
     stage = al256(bb * (size_t)P->p);
     X.wide_n = mvxi_wide_temps(P);
     X.wide_slot = al256((size_t)b * mvxi_wide_esize(P) + SLOT_STAGGER);
-    X.wide_off = stage + (mvxi_acc32(P->op) ? mvxi_wide_residue(P, J->send[0]) : 0);
+    X.wide_off = stage + (mvxi_wide_f32(P) ? mvxi_wide_residue(P, J->send[0]) : 0);
     if ((rc = mvxi_grow_pool(c, X.wide_off + X.wide_slot * (size_t)X.wide_n))) return rc;
     c->ran_exch = MVX_EXCH_COLL;
     if ((rc = mvxi_tev(c, 0, st))) return rc;

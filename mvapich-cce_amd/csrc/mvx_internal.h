@@ -333,6 +333,8 @@ typedef struct {           /* struct MPIR_OP, include/mpiops.h:1-11 */
 MVXI int mvxi_predefined(MPI_Op op);
 /* the extension ops MVX_SUM_ACC32 / MVX_PROD_ACC32 (predefined too) */
 static inline int mvxi_acc32(MPI_Op op) { return op == MVX_SUM_ACC32 || op == MVX_PROD_ACC32; }
+/* the ranks' mean MVX_AVG (predefined too): MPI_SUM's program divided once */
+static inline int mvxi_avg(MPI_Op op) { return op == MVX_AVG; }
 MVXI mvx_op_t *mvxi_user_op(MPI_Op op);
 MVXI int mvxi_op_kind(MPI_Op op);
 MVXI int mvxi_op_verdict(MPI_Op op, MPI_Datatype dt);
@@ -348,11 +350,14 @@ MVXI int mvxi_wide_temps(const mvx_plan *P);
  * for leaves aligned like `like`: the leaves' own residue mod 16, or for f32
  * slots the one that puts the first whole word of narrow elements on a
  * 16-byte boundary of the floats (mvx_ops.hip: split, split_f32) */
-static inline size_t mvxi_wide_esize(const mvx_plan *P) { return mvxi_acc32(P->op) ? 4 : (size_t)P->esize; }
+/* the plan's intermediates are f32 temporaries: the f32-accumulating ops, and
+ * MVX_AVG on the narrow floats (its other types are 4 and 8 bytes) */
+static inline int mvxi_wide_f32(const mvx_plan *P) { return mvxi_acc32(P->op) || (mvxi_avg(P->op) && P->esize < 4); }
+static inline size_t mvxi_wide_esize(const mvx_plan *P) { return mvxi_wide_f32(P) ? 4 : (size_t)P->esize; }
 static inline size_t mvxi_wide_residue(const mvx_plan *P, const void *like)
 {
     size_t head;
-    if (!mvxi_acc32(P->op)) return (uintptr_t)like & 15;
+    if (!mvxi_wide_f32(P)) return (uintptr_t)like & 15;
     head = ((4 - ((uintptr_t)like & 3)) & 3) / (size_t)P->esize;
     return (16 - 4 * head) & 15;
 }

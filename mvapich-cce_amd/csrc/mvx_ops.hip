@@ -5,7 +5,7 @@
 // never touch the device or a buffer; run() is the one place that launches.
 // mvx_op_plan answers with the plan alone.  The kernels are in mvx_ops_kern.h
 // (design notes at its top), their host-side tables in mvx_ops_tab.h and
-// mvx_ops_{cmp,arith,logic,loc,half,fp8,acc32}.hip.
+// mvx_ops_{cmp,arith,logic,loc,half,fp8,acc32,avg}.hip.
 #include <stdlib.h>
 
 #include "mvx_dtype.h"
@@ -105,9 +105,9 @@ static int ekind(int dtype)
 // Returns the kernel set, or NULL with *rc set to the reference's answer for
 // that (op, type): 329 where the op's switch has no case for it
 // (global_ops.c:158-161 and every sibling default), and MPI_ERR_OP for a
-// handle outside MPI_MAX..MPI_MAXLOC that is not one of the two extension
-// ops.  Those (MVX_SUM_ACC32, MVX_PROD_ACC32) have a case for the four
-// narrow floating types alone.
+// handle outside MPI_MAX..MPI_MAXLOC that is not one of the extension
+// ops.  MVX_SUM_ACC32 and MVX_PROD_ACC32 have a case for the four
+// narrow floating types alone; MVX_AVG has those and the f32 / f64 kinds.
 static bool acc32(int op) { return op == MVX_SUM_ACC32 || op == MVX_PROD_ACC32; }
 
 static const KSet *lookup(int op, int dtype, int *rc)
@@ -115,6 +115,7 @@ static const KSet *lookup(int op, int dtype, int *rc)
     int ek = ekind(dtype);
     *rc = MVX_ERR_OP_NOT_DEFINED;
     if (acc32(op)) return lookup_acc32(op, ek);
+    if (op == MVX_AVG) return lookup_avg(ek);
     if (ek == EK_LOGICAL && (op == MPI_BAND || op == MPI_BOR || op == MPI_BXOR))
         ek = EK_U32;                 // bitwise on the MPI_Fint word
     if (ek == EK_F16 || ek == EK_BF16) {
@@ -310,6 +311,7 @@ static int run(const Plan &pl, const Params &P, hipStream_t stream)
         B.dst = reinterpret_cast<u32x4 *>(P.dst);
         B.nvec = P.nvec;
         B.k = P.k;
+        B.divisor = P.divisor;
         args[0] = &B;
     }
     hipError_t e = hipLaunchKernel(pl.fn, dim3(pl.blocks), dim3(256), args, pl.lds, stream);
@@ -338,6 +340,7 @@ static int program_params(int op, int dtype, const void *const *srcs, const void
     for (int q = 0; q < k; ++q) {
         P.src[q] = (const char *)srcs[q];
         P.fold[q] = fold ? (const char *)fold[q] : nullptr;
+        P.divisor += 1 + (P.fold[q] != nullptr);   /* MVX_AVG: the leaves given (mvx_op_program_avg: its argument) */
     }
     P.dst = (char *)dst;
     P.n = (long)n;
@@ -426,6 +429,7 @@ extern "C" int mvx_op_apply(int op, int dtype, const void *in, void *inout,
     P.dst = (char *)inout;
     P.n = (long)n;
     P.k = 2;
+    P.divisor = 2;
     return run(plan_params(ks, P), P, (hipStream_t)stream);
 }
 
@@ -457,6 +461,27 @@ extern "C" int mvx_op_program_f32(int op, int dtype, const void *const *srcs, co
     }
     if (side == MVX_F32_OUT && ((uintptr_t)P.dst & 3)) return MPI_ERR_ARG;
     return run(plan_f32(ks, P, side == MVX_F32_OUT, config()), P, (hipStream_t)stream);
+}
+
+extern "C" int mvx_op_program_avg(int dtype, const void *const *srcs, const void *const *fold, int k,
+                                  unsigned tree_mask, unsigned chain_mask, void *dst, size_t n, int side,
+                                  int divisor, void *stream)
+{
+    const KSet *ks;
+    Params P;
+    int rc = program_params(MVX_AVG, dtype, srcs, fold, k, tree_mask, chain_mask, dst, n, &ks, P);
+    if (rc != MPI_SUCCESS) return rc;
+    if (divisor < 1 || (side != 0 && side != MVX_F32_IN)) return MPI_ERR_ARG;
+    if (side == MVX_F32_IN) {
+        /* only the narrow types have f32 temporaries; those are floats, 4-byte
+         * aligned and never folded (mvx_op_program_f32) */
+        if (!lookup(MVX_AVG, dtype, &rc)->f32side[1].fn) return MPI_ERR_ARG;
+        for (int q = 0; q < k; ++q)
+            if ((fold && fold[q]) || ((uintptr_t)srcs[q] & 3)) return MPI_ERR_ARG;
+    }
+    if (!ks) return MPI_SUCCESS;
+    P.divisor = divisor;
+    return run(side ? plan_f32(ks, P, false, config()) : plan_params(ks, P), P, (hipStream_t)stream);
 }
 
 extern "C" int mvx_op_plan(int op, int dtype, const void *const *srcs, const void *const *fold, int k,

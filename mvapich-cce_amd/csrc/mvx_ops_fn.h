@@ -3,7 +3,8 @@
 // chunks (what one lane moves per operand per step): element layouts, F<op, T>,
 // Chunk / CG, the chunk op CF with its SWAR, packed-16 and 8-bit float forms.
 // Last, the wide accumulator of the f32-accumulating ops (Wide, acc_steps,
-// acc_chunk).  Device code only; the kernels that use them are in
+// acc_chunk) and MVX_AVG's finalising division (avg_fin, avg_chunk).  Device
+// code only; the kernels that use them are in
 // mvx_ops_kern.h (design notes there).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -17,7 +18,11 @@ enum { OMAX = 0, OMIN, OSUM, OPROD, OLAND, OBAND, OLOR, OBOR, OLXOR, OBXOR,
        OMINLOC, OMAXLOC,
        // extension (MVX_SUM_ACC32 / MVX_PROD_ACC32): the whole combine program
        // in binary32, narrowed once (the end of this file)
-       OSUMA, OPRODA };
+       OSUMA, OPRODA,
+       // extension (MVX_AVG): the SUM program's value divided once by the rank
+       // contributions it consumed (the end of this file)
+       OAVG };
+static_assert(OAVG == 14, "");
 
 // Element layouts: the reference's C types on x86-64 LP64.
 struct cf32 { float re, im; };                          // global_ops.c:43-46
@@ -553,13 +558,43 @@ template <int O> struct CF<O, f8e5m2> {
 // at a time -- Wide<T>::L f32 lanes per leaf, 4 for the 8-bit types and 2 for
 // the 16-bit ones -- so 8 leaves x U chunks stay within the registers the
 // per-step tree bodies use.
-template <int O> struct acc_op { static constexpr bool v = O == OSUMA || O == OPRODA; };
+//
+// MVX_AVG (OAVG), the ranks' mean: MPI_SUM's program, its value divided once
+// by the number of rank contributions the whole program consumed (leaves plus
+// fold partners; Params::divisor), then stored.  On float and double the
+// program is F<OSUM, T>'s, step for step, and the division one correctly
+// rounded IEEE division in T (a plain `/`: nothing here or in the Makefile
+// allows a reciprocal or an approximate one; subnormals kept).  On the four
+// narrow types the program is the f32 one above with accf = add, divided in
+// binary32 and narrowed once -- the mean of eight E4M3 448s is 448, where the
+// sum, per step or in f32, has no value to narrow to.  A divisor of 1 divides
+// nothing, so a lone leaf keeps its bits.
+template <typename T> struct narrow_float {
+    static constexpr bool v = std::is_same<T, f16>::value || std::is_same<T, bf16>::value ||
+                              std::is_same<T, f8e4m3>::value || std::is_same<T, f8e5m2>::value;
+};
+// the (op, type) pairs whose program runs on widened f32 values
+template <int O, typename T> struct acc_op {
+    static constexpr bool v = O == OSUMA || O == OPRODA || (O == OAVG && narrow_float<T>::v);
+};
 
 template <int O>
 __device__ __forceinline__ float accf(float a, float b)
 {
-    static_assert(acc_op<O>::v, "");
-    return O == OSUMA ? a + b : a * b;
+    static_assert(O == OSUMA || O == OPRODA || O == OAVG, "");
+    return O == OPRODA ? a * b : a + b;
+}
+
+template <> struct F<OAVG, float> : F<OSUM, float> {};
+template <> struct F<OAVG, double> : F<OSUM, double> {};
+
+// the finalising step between the program and the single store (V: float or
+// double); every op but OAVG passes its value through
+template <int O, typename V>
+__device__ __forceinline__ V avg_fin(V y, int divisor)
+{
+    if constexpr (O == OAVG) return divisor == 1 ? y : y / (V)divisor;
+    else return y;
 }
 
 // one word of a chunk <-> its L elements as f32 lanes
@@ -683,10 +718,10 @@ __device__ __forceinline__ void acc_steps(float (&y)[KMAX][L], int k, unsigned t
 
 // One chunk of every leaf: x[0] = narrow(program(widen(x[q]) op widen(xf[q])
 // where fold_mask has bit q)), a word at a time.  Leaves q >= k are never
-// read (PROG = 1: k = KMAX).
+// read (PROG = 1: k = KMAX).  OAVG divides the f32 value before narrowing it.
 template <int O, typename T, int KMAX, int PROG>
 __device__ __forceinline__ void acc_chunk(Chunk<T> (&x)[KMAX], const Chunk<T> (&xf)[KMAX], unsigned fold_mask,
-                                          int k, unsigned tree_mask, unsigned chain_mask)
+                                          int k, unsigned tree_mask, unsigned chain_mask, int divisor)
 {
     constexpr int L = Wide<T>::L;
 #pragma unroll
@@ -705,7 +740,20 @@ __device__ __forceinline__ void acc_chunk(Chunk<T> (&x)[KMAX], const Chunk<T> (&
             }
         }
         acc_steps<O, KMAX, L, PROG>(y, k, tree_mask, chain_mask);
+#pragma unroll
+        for (int j = 0; j < L; ++j) y[0][j] = avg_fin<O>(y[0][j], divisor);
         x[0].w[w] = Wide<T>::narrow(y[0]);
+    }
+}
+
+// OAVG on float and double: the finalising step on every element of the
+// chunk that holds the per-step program's result
+template <int O, typename T>
+__device__ __forceinline__ void avg_chunk(Chunk<T> &x, int divisor)
+{
+    if constexpr (O == OAVG) {
+#pragma unroll
+        for (int j = 0; j < CG<T>::v; ++j) x.e[j] = avg_fin<O>(x.e[j], divisor);
     }
 }
 

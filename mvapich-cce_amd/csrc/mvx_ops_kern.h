@@ -3,7 +3,7 @@
 // path and what they take (Params, BodyParams), written for gfx950 (CDNA4,
 // wave64).  The ops on elements and chunks are in mvx_ops_fn.h; the host-side
 // tables that name every instantiation are in mvx_ops_tab.h, which mvx_ops.hip
-// and the per-op table units mvx_ops_{cmp,arith,logic,loc,half,fp8,acc32}.hip include.
+// and the per-op table units mvx_ops_{cmp,arith,logic,loc,half,fp8,acc32,avg}.hip include.
 // Built into libmvx_hip.so; C-ABI in include/mvx_hip.h.
 //
 // One kernel template covers every predefined op x type of the reference
@@ -35,7 +35,7 @@
 namespace mvx {
 
 // ---------------------------------------------------------------------------
-// launch parameters (passed by value, ~170 bytes of kernarg)
+// launch parameters (passed by value, ~180 bytes of kernarg)
 
 struct Params {
     const char *src[MVX_COMBINE_KMAX];
@@ -48,6 +48,7 @@ struct Params {
     int vec_ok;  // all pointers share their alignment mod 16
     unsigned tree_mask;   // bit l*8+q: y[q] = op(y[q], y[q + 2^l]), levels 0..2
     unsigned chain_mask;  // bit q (q >= 1): y[0] = op(y[0], y[q]) after the tree
+    int divisor;          // OAVG alone reads it: the rank contributions of the whole program
 };
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));  // one dwordx4
@@ -82,11 +83,12 @@ __device__ __forceinline__ void reduce_leaves(T (&y)[KMAX], int k, unsigned tree
 // the same element of every leaf through the f32-accumulating program
 // (acc_op): widened, folded and combined in f32, narrowed once.  A single
 // unfolded leaf has no step: it is copied, bits and all (a NaN's payload
-// would not survive the way to f32 and back), as the per-step ops copy it.
+// would not survive the way to f32 and back), as the per-step ops copy it
+// (OAVG: unless it is to be divided).
 template <int O, typename T, int KMAX>
 __device__ __forceinline__ void scalar_elem_acc(const Params &P, long i)
 {
-    if (P.k == 1 && !P.fold[0]) {
+    if (P.k == 1 && !P.fold[0] && (O != OAVG || P.divisor == 1)) {
         store_elt(reinterpret_cast<T *>(P.dst) + i, reinterpret_cast<const T *>(P.src[0])[i]);
         return;
     }
@@ -99,13 +101,13 @@ __device__ __forceinline__ void scalar_elem_acc(const Params &P, long i)
         }
     }
     acc_steps<O, KMAX, 1, 0>(y, P.k, P.tree_mask, P.chain_mask);
-    narrow_elt(reinterpret_cast<T *>(P.dst) + i, y[0][0]);
+    narrow_elt(reinterpret_cast<T *>(P.dst) + i, avg_fin<O>(y[0][0], P.divisor));
 }
 
 template <int O, typename T, int KMAX>
 __device__ __forceinline__ void scalar_elem(const Params &P, long i)
 {
-    if constexpr (acc_op<O>::v) {
+    if constexpr (acc_op<O, T>::v) {
         scalar_elem_acc<O, T, KMAX>(P, i);
     } else {
         T y[KMAX];
@@ -117,6 +119,7 @@ __device__ __forceinline__ void scalar_elem(const Params &P, long i)
             }
         }
         reduce_leaves<O, T, KMAX>(y, P.k, P.tree_mask, P.chain_mask);
+        if constexpr (O == OAVG) y[0] = avg_fin<O>(y[0], P.divisor);
         store_elt(reinterpret_cast<T *>(P.dst) + i, y[0]);
     }
 }
@@ -174,7 +177,7 @@ __device__ __forceinline__ void st_chunk(u32x4 *base, long c, const Chunk<T> &x)
 // evaluated in f32 (acc_chunk), the result left in x[u][0].
 template <int O, typename T, int KMAX, int U, int NT, int PROG>
 __device__ __forceinline__ void batch_acc(Chunk<T> (&x)[U][KMAX], const u32x4 *(&fold)[KMAX], long c0,
-                                          long nvec, int k, unsigned tree_mask, unsigned chain_mask)
+                                          long nvec, int k, unsigned tree_mask, unsigned chain_mask, int divisor)
 {
     Chunk<T> xf[U][KMAX];
     unsigned fmask = 0;
@@ -191,9 +194,10 @@ __device__ __forceinline__ void batch_acc(Chunk<T> (&x)[U][KMAX], const u32x4 *(
             }
         }
     }
-    if (PROG == 0 && k == 1 && !fmask) return;     // a lone leaf is copied as it is (scalar_elem_acc)
+    // a lone leaf is copied as it is (scalar_elem_acc)
+    if (PROG == 0 && k == 1 && !fmask && (O != OAVG || divisor == 1)) return;
 #pragma unroll
-    for (int u = 0; u < U; ++u) acc_chunk<O, T, KMAX, PROG>(x[u], xf[u], fmask, k, tree_mask, chain_mask);
+    for (int u = 0; u < U; ++u) acc_chunk<O, T, KMAX, PROG>(x[u], xf[u], fmask, k, tree_mask, chain_mask, divisor);
 }
 
 // PROG = 0: the program comes from the masks (any chain of trees over
@@ -249,8 +253,8 @@ k_combine(const Params P)
                     if (PROG == 1 || q < k) x[u][q] = ld_chunk<T, NT>(src[q], c);
             }
         }
-        if constexpr (acc_op<O>::v) {
-            batch_acc<O, T, KMAX, U, NT, PROG>(x, fold, c0, P.nvec, k, tmask, cmask);
+        if constexpr (acc_op<O, T>::v) {
+            batch_acc<O, T, KMAX, U, NT, PROG>(x, fold, c0, P.nvec, k, tmask, cmask, P.divisor);
         } else {
 #pragma unroll
             for (int q = 0; q < KMAX; ++q) {
@@ -306,6 +310,9 @@ k_combine(const Params P)
                     }
                 }
             }
+            // OAVG: the program's value divided once
+#pragma unroll
+            for (int u = 0; u < U; ++u) avg_chunk<O, T>(x[u][0], P.divisor);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -327,6 +334,7 @@ struct BodyParams {
     u32x4 *dst;
     long nvec;   // chunks
     int k;       // leaves (k_chain_body<..., 8, ...>: 5 to 8)
+    int divisor; // Params::divisor
 };
 
 // 56 KiB of static LDS per block: 2 resident blocks (8 waves) per CU.
@@ -361,14 +369,15 @@ k_tree_body(const BodyParams P)
         for (int u = 0; u < U; ++u) {
             const long c = c0 + (long)u * 256;
             if (c < P.nvec) {
-                if constexpr (acc_op<O>::v) {
-                    acc_chunk<O, T, KMAX, 1>(x[u], x[u], 0u, KMAX, 0u, 0u);
+                if constexpr (acc_op<O, T>::v) {
+                    acc_chunk<O, T, KMAX, 1>(x[u], x[u], 0u, KMAX, 0u, 0u, P.divisor);
                 } else {
 #pragma unroll
                     for (int h = 1; h < KMAX; h <<= 1)
 #pragma unroll
                         for (int q = 0; q + h < KMAX; q += 2 * h)
                             CF<O, T>::f(x[u][q], x[u][q + h]);
+                    avg_chunk<O, T>(x[u][0], P.divisor);
                 }
                 st_chunk<T, BODY_ST_NT>(P.dst, c, x[u][0]);
             }
@@ -403,12 +412,13 @@ k_chain_body(const BodyParams P)
         for (int u = 0; u < U; ++u) {
             const long c = c0 + (long)u * 256;
             if (c < P.nvec) {
-                if constexpr (acc_op<O>::v) {
-                    acc_chunk<O, T, KMAX, 0>(x[u], x[u], 0u, k, 0u, (1u << k) - 2u);
+                if constexpr (acc_op<O, T>::v) {
+                    acc_chunk<O, T, KMAX, 0>(x[u], x[u], 0u, k, 0u, (1u << k) - 2u, P.divisor);
                 } else {
 #pragma unroll
                     for (int q = 1; q < KMAX; ++q)
                         if (q < k) CF<O, T>::f(x[u][0], x[u][q]);
+                    avg_chunk<O, T>(x[u][0], P.divisor);
                 }
                 st_chunk<T, BODY_ST_NT>(P.dst, c, x[u][0]);
             }
@@ -420,7 +430,7 @@ k_chain_body(const BodyParams P)
 // program over more than 8 leaves is cut into (mvx_combine.c), its
 // intermediates being f32 temporaries.  DIR = 0: narrow leaves (folds
 // allowed), f32 result, not narrowed; DIR = 1: f32 leaves, the result narrowed
-// once.  A lane takes one 32-bit word of each narrow operand against L floats
+// once (OAVG, the last launch of such a program: divided, then narrowed).  A lane takes one 32-bit word of each narrow operand against L floats
 // of each f32 one (a dwordx4 for the 8-bit types, a dwordx2 for the 16-bit
 // ones).  Params: head elements lead to nvec such words where the narrow
 // side is 4-byte and the f32 side 4 * L-byte aligned (vec_ok), else every
@@ -457,6 +467,7 @@ k_combine_f32(const Params P)
                 }
             }
             acc_steps<O, KMAX, 1, 0>(y, k, tmask, cmask);
+            y[0][0] = avg_fin<O>(y[0][0], P.divisor);
             if constexpr (DIR == 0) reinterpret_cast<float *>(P.dst)[i] = y[0][0];
             else narrow_elt(reinterpret_cast<T *>(P.dst) + i, y[0][0]);
         }
@@ -484,6 +495,8 @@ k_combine_f32(const Params P)
             }
         }
         acc_steps<O, KMAX, L, 0>(y, k, tmask, cmask);
+#pragma unroll
+        for (int j = 0; j < L; ++j) y[0][j] = avg_fin<O>(y[0][j], P.divisor);
         if constexpr (DIR == 0) {
             fL v;
 #pragma unroll

@@ -3,7 +3,7 @@
 // (Config), the descriptor of one kernel instantiation (KVar), the families
 // and sets built from them, the element kinds and the per-op table units'
 // lookup functions.  Included by mvx_ops.hip (dispatch and launch policy) and
-// by mvx_ops_{cmp,arith,logic,loc,half,fp8,acc32}.hip, which instantiate the kernels of
+// by mvx_ops_{cmp,arith,logic,loc,half,fp8,acc32,avg}.hip, which instantiate the kernels of
 // mvx_ops_kern.h through the macros below, one translation unit each so that
 // they compile in parallel.
 #include <stdio.h>
@@ -108,6 +108,7 @@ struct KSet {
     KFam tree8, tree4;     // PROG = 1: full trees over 8 / 4 leaves
     KFam chain8, chain4;   // full chains over 8 / 4 leaves: k_chain_body, else the masked program
     KVar f32side[2];       // the f32-accumulating ops: k_combine_f32, f32 result [0] / f32 leaves [1]; else empty
+                           // (MVX_AVG on the narrow floats: [1] alone)
     int esize;
     int chunk;             // bytes per chunk (16, or the element if wider)
     const char *name;
@@ -206,8 +207,10 @@ static KSet kset(const char *name)
         s.prog2 = {};
     }
     s.f32side[0] = s.f32side[1] = KVar{};
-    if constexpr (acc_op<O>::v) {
-        s.f32side[0] = {(const void *)&k_combine_f32<O, T, 0>, &ksym<K_COMBINE_F32, O, T, 0>, 1, false, 1, 0, 1, MVX_COMBINE_KMAX};
+    if constexpr (acc_op<O, T>::v) {
+        // (MVX_AVG's launches before the last are MVX_SUM_ACC32's: it has the f32-leaves form alone)
+        if constexpr (O != OAVG)
+            s.f32side[0] = {(const void *)&k_combine_f32<O, T, 0>, &ksym<K_COMBINE_F32, O, T, 0>, 1, false, 1, 0, 1, MVX_COMBINE_KMAX};
         s.f32side[1] = {(const void *)&k_combine_f32<O, T, 1>, &ksym<K_COMBINE_F32, O, T, 1>, 1, false, 1, 0, 1, MVX_COMBINE_KMAX};
     }
     s.esize = (int)sizeof(T);
@@ -286,5 +289,6 @@ const KSet *lookup_loc(int op, int ek);     // MAXLOC, MINLOC     mvx_ops_loc.hi
 const KSet *lookup_half(int op, int ek);    // every op on the 16-bit floats  mvx_ops_half.hip
 const KSet *lookup_fp8(int op, int ek);     // every op on the 8-bit floats   mvx_ops_fp8.hip
 const KSet *lookup_acc32(int op, int ek);   // MVX_SUM_ACC32, MVX_PROD_ACC32  mvx_ops_acc32.hip
+const KSet *lookup_avg(int ek);             // MVX_AVG                        mvx_ops_avg.hip
 
 }  // namespace mvx

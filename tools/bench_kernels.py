@@ -17,7 +17,8 @@ the launch stream), GB/s and fraction of the 8 TB/s HBM peak.
 Modes (arguments): sweep, all, all-tree, ks, x87 add lines to the four
 configs; half runs only the 16-bit floating types against MPI_SHORT, fp8 only
 the 8-bit ones against MPI_UNSIGNED_CHAR, acc32 only MVX_SUM_ACC32 /
-MVX_PROD_ACC32 against MPI_SUM / MPI_PROD on the four narrow floating types.
+MVX_PROD_ACC32 against MPI_SUM / MPI_PROD on the four narrow floating types,
+avg only MVX_AVG's 8-leaf tree against its sum twin (f32, E4M3).
 """
 import importlib
 import json
@@ -137,8 +138,23 @@ def acc32(mvx):
                 run(mvx, "W4-%s-%s-%s" % (on, tn, kind), op, t, 4, 1, 256 * MIB, 2, reps=10, warm=2)
 
 
+def avg(mvx):
+    """MVX_AVG next to the sum it divides, the 8-leaf tree at 64 MiB leaves:
+    avg_f32 beside sum_f32, avg_f8e4m3 beside sum_acc32_f8e4m3, each pair
+    three times over so the twin's own run-to-run spread stands next to the
+    difference.  Both move the same bytes; the mean adds one division an
+    element."""
+    for rep in range(3):
+        for t, tn, twin in ((mvx.MPI_FLOAT, "f32", mvx.MPI_SUM), (72, "e4m3", mvx.MVX_SUM_ACC32)):
+            for op, kind in ((twin, "sum"), (mvx.MVX_AVG, "avg")):
+                run(mvx, "M8-%s-%s-%d" % (kind, tn, rep), op, t, 8, 0, 64 * MIB, 2, reps=10, warm=2)
+
+
 def main():
     mvx = importlib.import_module("mvapich-cce_amd")
+    if "avg" in sys.argv[1:]:
+        avg(mvx)
+        return
     if "acc32" in sys.argv[1:]:
         acc32(mvx)
         return
