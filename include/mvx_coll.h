@@ -226,6 +226,28 @@ int mvx_op_create_device(MVX_Device_function *function, int commute, MPI_Op *op)
  * MPI library's (libmvx_embed.so exports only mvx_* names) */
 int mvx_op_create(MPI_User_function *function, int commute, MPI_Op *op);
 int mvx_op_free(MPI_Op *op);
+/* EXTENSION: a per-rank scaled SUM for tensors that travel as narrow floats
+ * plus a scale (RCCL's ncclRedOpCreatePreMulSum, with the amax it lacks).
+ * Over the rank's combine program, exactly as MVX_SUM_ACC32 evaluates it:
+ * every contribution is widened exactly to binary32 and multiplied by
+ * rank_scale[r] of the rank r it came from (one f32 multiply); the steps are
+ * f32 adds in the plan's order; the value is multiplied once by out_scale,
+ * and narrowed once (stored as it is on MPI_FLOAT).  If amax_dev is not NULL
+ * it is a 4-byte aligned device word into which each call combines, by an
+ * atomic unsigned maximum, bits(v) & 0x7fffffff of the largest |v| among the
+ * f32 values this rank's combine is about to narrow -- its own block's; a
+ * NaN leaves a NaN word.  The caller zeroes the word, the library never does.
+ * Defined on MVX_FLOAT16, MVX_BFLOAT16, MVX_FLOAT8_E4M3, MVX_FLOAT8_E5M2,
+ * MPI_FLOAT and MPI_REAL; every other type answers 329 like any undefined
+ * pair.  The handle comes from the user-op table (MPI_Op_free frees it) and
+ * holds its own copy of the scales; it is planned as a predefined commutative
+ * op, MPI_SUM's plan.  Every rank must pass the same rank_scale[] (not
+ * checked).  nranks is 1 to 64; a call on a communicator of another size
+ * returns MPI_ERR_ARG on every rank before anything is exchanged.  Scales
+ * may be negative or non-finite: the arithmetic above defines the result.
+ * Such calls always run directly, never from a captured graph. */
+int mvx_op_create_scaled_sum(const float *rank_scale, int nranks, float out_scale,
+                             void *amax_dev /* 4-byte aligned device word, or NULL */, MPI_Op *op);
 /* GPUs visible to this process */
 int mvx_device_count(void);
 int MPI_Error_class(int errorcode, int *errorclass);

@@ -78,6 +78,9 @@ int mvx_coll_scan(void *sendbuf, void *recvbuf, int count, int datatype, int op,
 typedef void(mvx_user_function)(void *invec, void *inoutvec, int *len, int *datatype);
 int mvx_op_create(mvx_user_function *function, int commute, int *op);
 int mvx_op_free(int *op);
+/* a per-rank scaled SUM with a fused amax (mvx_coll.h has the semantics);
+ * mvx_op_free frees the handle */
+int mvx_op_create_scaled_sum(const float *rank_scale, int nranks, float out_scale, void *amax_dev, int *op);
 
 /* The datatype handle a user function receives for libmvx type `type`
  * (default: `type` itself).  A binding that rebuilds the host MPI's derived

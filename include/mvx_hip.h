@@ -49,7 +49,7 @@ extern "C" {
  * MVX_FLOAT16 / MVX_BFLOAT16 / MVX_FLOAT8_E4M3 / MVX_FLOAT8_E5M2 (mvx_mpi.h),
  * which have MPI_FLOAT's seven ops and, alone, the two extension ops
  * MVX_SUM_ACC32 / MVX_PROD_ACC32; MVX_AVG has those four and the f32 / f64
- * types. */
+ * types; MVX_SCALED_SUM (below) those four and MPI_FLOAT / MPI_REAL. */
 int mvx_op_supported(int op, int dtype);
 /* Bytes of one element as the (op, dtype) kernel reads it (the C pair
  * struct for MAXLOC / MINLOC on a struct type), or 0 if undefined. */
@@ -198,6 +198,35 @@ int mvx_op_program_f32(int op, int dtype, const void *const *srcs,
 int mvx_op_program_avg(int dtype, const void *const *srcs, const void *const *fold,
                        int k, unsigned tree_mask, unsigned chain_mask, void *dst,
                        size_t n, int side, int divisor, void *hip_stream);
+
+/* The per-rank scaled sum, a device-layer op index (at the MPI layer 169 is
+ * MPI_ERR_OP: there the op is a handle of mvx_op_create_scaled_sum,
+ * mvx_coll.h).  MVX_SUM_ACC32's program on binary32 values, except that every
+ * leaf and fold partner, once widened, is multiplied by a scale of its own
+ * (one f32 multiply), the program's value is multiplied once by out_scale,
+ * and -- where amax_dev is not NULL -- the largest magnitude of the stored
+ * elements' f32 values before the single narrowing is combined into the
+ * 4-byte aligned device word amax_dev by an atomic unsigned maximum of
+ * bits(v) & 0x7fffffff (a NaN result leaves a NaN word).  The caller zeroes
+ * the word; no call ever does.  Defined on the four narrow floating types
+ * and on MPI_FLOAT / MPI_REAL (stored as it is); every other type is 329.
+ * A lone unfolded leaf whose scale and out_scale are 1 is copied, bits and
+ * all, and still counts for amax.  Through mvx_op_apply, mvx_op_program and
+ * mvx_op_program_f32 the op runs with every scale 1 and no amax: the bits of
+ * MVX_SUM_ACC32 (of MPI_SUM on MPI_FLOAT).  The full form:
+ *   side 0          : leaves and dst of dtype.
+ *   side MVX_F32_OUT: dst n floats; the leaves' scales are applied, out_scale
+ *                     and amax_dev are ignored.
+ *   side MVX_F32_IN : leaves n floats each, never folded; leaf_scale is
+ *                     ignored, out_scale, amax and the narrowing are applied.
+ * leaf_scale has k entries; fold_scale, k entries, may be NULL when no leaf
+ * is folded.  Return codes of mvx_op_program_f32; MPI_ERR_ARG also for a
+ * missing scale array or a misaligned amax_dev. */
+#define MVX_SCALED_SUM 169
+int mvx_op_program_scaled(int dtype, const void *const *srcs, const void *const *fold, int k,
+                          unsigned tree_mask, unsigned chain_mask, void *dst, size_t n, int side,
+                          const float *leaf_scale, const float *fold_scale, float out_scale,
+                          void *amax_dev, void *hip_stream);
 
 /* What mvx_op_program would launch for these arguments, without launching:
  * the same checks and return codes, then the kernel template as rocprofv3

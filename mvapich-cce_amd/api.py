@@ -10,8 +10,8 @@ from . import coll, hip
 from .consts import COLL_ALLREDUCE, COLL_REDUCE, COLL_REDUCE_SCATTER  # noqa: F401
 
 __all__ = [
-    "addr", "stream_handle", "op_apply", "op_combine", "op_program", "op_program_f32", "op_program_avg", "op_plan", "LaunchPlan", "Comm",
-    "MPI_Allreduce", "MPI_Reduce", "MPI_Reduce_scatter", "MPI_Scan", "MPI_Op_create", "MPI_Op_free", "op_create_device",
+    "addr", "stream_handle", "op_apply", "op_combine", "op_program", "op_program_f32", "op_program_avg", "op_program_scaled", "op_plan", "LaunchPlan", "Comm",
+    "MPI_Allreduce", "MPI_Reduce", "MPI_Reduce_scatter", "MPI_Scan", "MPI_Op_create", "MPI_Op_free", "op_create_device", "op_create_scaled_sum",
     "MPIR_call", "op_errno", "last_kernel", "last_kernel_symbol", "last_launch", "set_launch",
     "set_fortran_logical", "comm_reap", "host_register_enable", "host_unregister", "host_register_stats",
     "host_hooks_active", "host_invalidate", "host_register_deferred",
@@ -86,6 +86,21 @@ def op_program_avg(dtype, srcs, dst, n, tree_mask, chain_mask, divisor, side=0, 
     fo = _pp(folds) if folds is not None else None
     return hip().mvx_op_program_avg(dtype, _pp(srcs), fo, len(srcs), tree_mask, chain_mask, addr(dst), n, side,
                                     divisor, stream_handle(stream))
+
+
+def op_program_scaled(dtype, srcs, dst, n, tree_mask, chain_mask, leaf_scale, out_scale=1.0, amax=None, side=0,
+                      folds=None, fold_scale=None, stream=None):
+    """MVX_SCALED_SUM's combine program (mvx_op_program_scaled): leaf q times
+    leaf_scale[q] (fold partners times fold_scale[q]), summed in f32, times
+    out_scale, narrowed once; `amax` is a 4-byte device word (tensor or
+    address) for max |v| before narrowing, or None.  side 0, F32_OUT or F32_IN
+    as in op_program_f32."""
+    fo = _pp(folds) if folds is not None else None
+    ls = (ctypes.c_float * len(srcs))(*leaf_scale)
+    fs = (ctypes.c_float * len(srcs))(*fold_scale) if fold_scale is not None else None
+    return hip().mvx_op_program_scaled(dtype, _pp(srcs), fo, len(srcs), tree_mask, chain_mask, addr(dst), n, side,
+                                       ls, fs, out_scale, addr(amax) if amax is not None else None,
+                                       stream_handle(stream))
 
 
 class LaunchPlan(ctypes.Structure):
@@ -399,6 +414,18 @@ def op_create_device(function_addr, commute):
     Returns (rc, op_handle)."""
     h = ctypes.c_int()
     rc = coll().mvx_op_create_device(ctypes.c_void_p(function_addr), commute, ctypes.byref(h))
+    return rc, h.value
+
+
+def op_create_scaled_sum(rank_scale, out_scale=1.0, amax=None, nranks=None):
+    """mvx_op_create_scaled_sum: a per-rank scaled SUM over len(rank_scale)
+    ranks (`nranks` overrides the count passed) with a fused amax into the
+    4-byte device word `amax` (tensor or address; None: no amax).  Returns
+    (rc, op_handle); MPI_Op_free frees the handle."""
+    h = ctypes.c_int(0)
+    rs = (ctypes.c_float * max(len(rank_scale), 1))(*rank_scale)
+    rc = coll().mvx_op_create_scaled_sum(rs, len(rank_scale) if nranks is None else nranks, out_scale,
+                                         addr(amax) if amax is not None else None, ctypes.byref(h))
     return rc, h.value
 
 

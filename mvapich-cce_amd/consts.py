@@ -29,6 +29,9 @@ MPI_LOR, MPI_BOR, MPI_LXOR, MPI_BXOR, MPI_MINLOC, MPI_MAXLOC = 106, 107, 108, 10
 MVX_SUM_ACC32, MVX_PROD_ACC32 = 164, 165
 # EXTENSION: the ranks' mean, MPI_SUM's result divided once (narrow floats: MVX_SUM_ACC32's f32 value)
 MVX_AVG = 168
+# device-layer op index (include/mvx_hip.h) of the per-rank scaled sum; at the MPI layer the op is a
+# handle of op_create_scaled_sum and 169 is MPI_ERR_OP
+MVX_SCALED_SUM = 169
 F32_OUT, F32_IN = 1, 2                       # mvx_op_program_f32's side (include/mvx_hip.h)
 
 MPI_COMM_WORLD, MPI_COMM_SELF = 91, 92
@@ -121,6 +124,8 @@ DEFINED_EXT8 = {op: list(_FP8S) for op in DEFINED_EXT}
 DEFINED_ACC32 = {op: _HALFS + _FP8S for op in (MVX_SUM_ACC32, MVX_PROD_ACC32)}
 # the mean: the f32 / f64 kinds and the four narrow floats, in a table of its own
 DEFINED_AVG = {MVX_AVG: [MPI_FLOAT, MPI_DOUBLE, MPI_REAL, MPI_DOUBLE_PRECISION] + _HALFS + _FP8S}
+# the scaled sum: the f32 kind and the four narrow floats (there is no f64 form: scales are floats)
+DEFINED_SCALED = {MVX_SCALED_SUM: [MPI_FLOAT, MPI_REAL] + _HALFS + _FP8S}
 DEVICE_TYPES = sorted(NP_DTYPE)
 
 # mvx_comm_set_call_kinds (include/mvx_embed.h)

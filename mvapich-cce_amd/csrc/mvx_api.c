@@ -72,6 +72,14 @@ static int plan_moves(const mvx_plan *P)
 
 static int run_on(mvx_comm_t *c, const call_t *k, hipStream_t st, int blocking);
 
+/* a scaled sum holds one scale per rank: on a communicator of another size
+ * every rank refuses the call before anything is exchanged */
+static int scaled_mismatch(MPI_Op op, int p)
+{
+    const mvx_op_t *o = mvxi_scaled(op);
+    return o && o->nranks != p;
+}
+
 /* every call runs on its communicator's device; the caller's stays current */
 static int run(mvx_comm_t *c, const call_t *k, hipStream_t st, int blocking)
 {
@@ -97,6 +105,7 @@ static int run_on(mvx_comm_t *c, const call_t *k, hipStream_t st, int blocking)
 
     if (c->local) return MPI_ERR_COMM;   /* virtual comms use *_multi */
     if (!w) return MPI_ERR_INTERN;
+    if (scaled_mismatch(k->op, c->size)) return MPI_ERR_ARG;
     Pp = &w->call_plan;
     c->ran_exch = -1;
     c->last_st = st;
@@ -372,6 +381,7 @@ static int run_multi_on(mvx_comm_t *c, int coll, void *const *sendbufs,
     c->last_st = st;
     for (r = 0; r < p; r++) rcs[r] = 0;
     if (!mvxi_predefined(op) && !mvxi_user_op(op)) { for (r = 0; r < p; r++) rcs[r] = MPI_ERR_OP; return MPI_SUCCESS; }
+    if (scaled_mismatch(op, p)) { for (r = 0; r < p; r++) rcs[r] = MPI_ERR_ARG; return MPI_SUCCESS; }
     for (r = 0; r < p; r++) {
         rc = mvx_plan_build_tuned(&plans[r], coll, p, r, count, recvcnts, dt, op, root, mvxi_op_kind(op),
                                   &c->tune);

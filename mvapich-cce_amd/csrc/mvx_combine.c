@@ -4,7 +4,8 @@
  * (mvx_op_program, libmvx_hip.so); wider programs run as groups of 8 with the
  * same association (the f32-accumulating extension ops through f32
  * temporaries, so nothing is narrowed before the end; MVX_AVG as its sum,
- * divided in the last launch); user functions get
+ * divided in the last launch; a scaled sum with its ranks' scales on the raw
+ * leaves and its output scale and amax in the last launch); user functions get
  * the reference's operand roles (host MPI_User_functions through pinned
  * scratch, device functions in HBM); datatypes with holes are unpacked to the extent layout the op sees.
  * Reference: the (*uop) calls of intra_fns_new.c (e.g. 5505-5512, 5681-5699)
@@ -114,7 +115,11 @@ static int combine_user(mvx_comm_t *c, const mvx_plan *P, const void *const *src
  * truncated group tree is the truncated tree's restriction (q + 2^l < m
  * within the last group), so the association is the reference's.  A CHAIN
  * runs in windows of 8 whose result is the next window's first value. */
-typedef struct { const void *p, *f; int wide; } leafref;   /* wide: an f32 temporary */
+typedef struct {
+    const void *p, *f;
+    int wide;        /* an f32 temporary */
+    float s, sf;     /* a scaled sum's raw leaf and fold partner: their ranks' scales */
+} leafref;
 
 /* (a scratch without a base is a dry run: slots are counted, nothing is
  * launched -- mvx_plan_wide_slots) */
@@ -141,7 +146,13 @@ static char *scratch_take(scratch_t *S)
  * for the narrow floats, so the temporaries, their slots and every launch
  * but the last are that op's.  The last launch (DST_LAST) divides by the
  * whole program's rank contributions, which a launch's own leaves no longer
- * tell: mvx_op_program_avg takes them as an argument. */
+ * tell: mvx_op_program_avg takes them as an argument.
+ *
+ * A scaled sum (mvx_op_create_scaled_sum) is MVX_SUM_ACC32's scheme with the
+ * same slots, on MPI_FLOAT too: every launch that reads raw leaves -- the
+ * 1-leaf widening one included -- multiplies them by their ranks' scales
+ * (MVX_F32_OUT), f32 to f32 rounds are MPI_SUM on MPI_FLOAT, and the last
+ * launch applies the output scale and takes amax. */
 #define DST_WIDE 1   /* dst takes the f32 value (a temporary of an f32-accumulating program) */
 #define DST_LAST 2   /* dst is the program's result */
 
@@ -158,7 +169,10 @@ static int launch_prog(const mvx_plan *P, leafref *v, int m, unsigned tmask,
     const void *srcs[MVX_COMBINE_KMAX], *fold[MVX_COMBINE_KMAX];
     const size_t n = (size_t)P->c_cnt;
     const int dst_wide = dflags & DST_WIDE, avg = mvxi_avg(P->op);
-    const int op = !avg ? P->op : mvxi_wide_f32(P) ? MVX_SUM_ACC32 : MPI_SUM;   /* every launch but AVG's last */
+    const mvx_op_t *sc = mvxi_scaled(P->op);
+    /* every launch but AVG's last; a scaled sum's f32 to f32 rounds */
+    const int op = sc ? MVX_SUM_ACC32 : !avg ? P->op : mvxi_wide_f32(P) ? MVX_SUM_ACC32 : MPI_SUM;
+    float ls[MVX_COMBINE_KMAX], fs[MVX_COMBINE_KMAX];
     int q, nw = 0, rc;
     if (!dst) return MPI_ERR_INTERN;
     for (q = 0; q < m; q++) nw += v[q].wide;
@@ -168,13 +182,23 @@ static int launch_prog(const mvx_plan *P, leafref *v, int m, unsigned tmask,
             char *t;
             if (v[q].wide) continue;
             if (!(t = scratch_take(S))) return MPI_ERR_INTERN;
-            if (S->base && (rc = mvx_op_program_f32(op, P->dtype, &v[q].p, &v[q].f, 1, 0u, 0u, t, n, MVX_F32_OUT, st)))
-                return rc;
+            if (S->base && sc)
+                rc = mvx_op_program_scaled(P->dtype, &v[q].p, &v[q].f, 1, 0u, 0u, t, n, MVX_F32_OUT, &v[q].s, &v[q].sf,
+                                           1.0f, NULL, st);
+            else if (S->base)
+                rc = mvx_op_program_f32(op, P->dtype, &v[q].p, &v[q].f, 1, 0u, 0u, t, n, MVX_F32_OUT, st);
+            else
+                rc = MPI_SUCCESS;
+            if (rc) return rc;
             v[q].p = t; v[q].f = NULL; v[q].wide = 1;
         }
     }
-    for (q = 0; q < m; q++) { srcs[q] = v[q].p; fold[q] = v[q].f; }
+    for (q = 0; q < m; q++) { srcs[q] = v[q].p; fold[q] = v[q].f; ls[q] = v[q].s; fs[q] = v[q].sf; }
     if (!S->base) return MPI_SUCCESS;
+    if (sc && !(nw && dst_wide))
+        return mvx_op_program_scaled(P->dtype, srcs, nw ? NULL : fold, m, tmask, cmask, dst, n,
+                                     dst_wide ? MVX_F32_OUT : nw ? MVX_F32_IN : 0, ls, fs,
+                                     (dflags & DST_LAST) ? sc->out_scale : 1.0f, (dflags & DST_LAST) ? sc->amax : NULL, st);
     if (avg && (dflags & DST_LAST))
         return mvx_op_program_avg(P->dtype, srcs, nw ? NULL : fold, m, tmask, cmask, dst, n, nw ? MVX_F32_IN : 0,
                                   avg_divisor(P), st);
@@ -199,7 +223,7 @@ static int tree_eval(const mvx_plan *P, leafref *v, int m, void *dst, int dflags
             if (len == 1 && !v[8 * g].f) { v[g] = v[8 * g]; continue; }
             t = scratch_take(S);
             if ((rc = launch_prog(P, v + 8 * g, len, mvx_tree_mask(len), 0u, t, acc, S, st))) return rc;
-            v[g].p = t; v[g].f = NULL; v[g].wide = acc;
+            v[g].p = t; v[g].f = NULL; v[g].wide = acc; v[g].s = v[g].sf = 1.0f;
         }
         m = ng;
     }
@@ -214,7 +238,7 @@ static int chain_eval(const mvx_plan *P, leafref *v, int m, void *dst, scratch_t
         char *t = scratch_take(S);
         if ((rc = launch_prog(P, v + i, 8, 0u, mvx_chain_mask(8), t, acc, S, st))) return rc;
         i += 7;
-        v[i].p = t; v[i].f = NULL; v[i].wide = acc;
+        v[i].p = t; v[i].f = NULL; v[i].wide = acc; v[i].s = v[i].sf = 1.0f;
     }
     return launch_prog(P, v + i, m - i, 0u, mvx_chain_mask(m - i), dst, DST_LAST, S, st);
 }
@@ -237,14 +261,20 @@ static int combine_wide(const mvx_plan *P, const void *const *srcs, const void *
                         void *dst, scratch_t *S, hipStream_t st)
 {
     leafref v[MVX_MAXK], heads[MVX_MAXK];
+    const mvx_op_t *sc = mvxi_scaled(P->op);
     int q, s, e, nh = 0, rc;
-    for (q = 0; q < P->k; q++) { v[q].p = srcs[q]; v[q].f = fold[q]; v[q].wide = 0; }
+    for (q = 0; q < P->k; q++) {
+        v[q].p = srcs[q]; v[q].f = fold[q]; v[q].wide = 0;
+        v[q].s = sc ? sc->rank_scale[P->leaf[q]] : 1.0f;
+        v[q].sf = sc && P->leaf_fold[q] >= 0 ? sc->rank_scale[P->leaf_fold[q]] : 1.0f;
+    }
     if (seg_end(P, 0) == P->k) return tree_eval(P, v, P->k, dst, DST_LAST, S, st);
     for (s = 0; s < P->k; s = e) {
         e = seg_end(P, s);
         if (e - s == 1) { heads[nh++] = v[s]; continue; }
         heads[nh].p = scratch_take(S);
         heads[nh].f = NULL;
+        heads[nh].s = heads[nh].sf = 1.0f;
         heads[nh].wide = mvxi_wide_f32(P);
         if ((rc = tree_eval(P, v + s, e - s, (void *)heads[nh].p, heads[nh].wide, S, st))) return rc;
         nh++;
@@ -340,6 +370,7 @@ int mvxi_combine(mvx_comm_t *c, const mvx_plan *P, const char *const *leafp, voi
                    scratch_t *S, hipStream_t st)
 {
     const void *srcs[MVX_MAXK], *fold[MVX_MAXK];
+    const mvx_op_t *sc;
     unsigned tm, cm;
     int q;
     for (q = 0; q < P->k; q++) {
@@ -361,5 +392,14 @@ int mvxi_combine(mvx_comm_t *c, const mvx_plan *P, const char *const *leafp, voi
         return combine_user(c, P, srcs, fold, dst, st, 0, (size_t)(P->c_cnt * P->esize));
     if (P->k > MVX_COMBINE_KMAX) return combine_wide(P, srcs, fold, dst, S, st);
     mvx_plan_masks(P, &tm, &cm);
+    if ((sc = mvxi_scaled(P->op))) {
+        float ls[MVX_COMBINE_KMAX], fs[MVX_COMBINE_KMAX];
+        for (q = 0; q < P->k; q++) {
+            ls[q] = sc->rank_scale[P->leaf[q]];
+            fs[q] = P->leaf_fold[q] >= 0 ? sc->rank_scale[P->leaf_fold[q]] : 1.0f;
+        }
+        return mvx_op_program_scaled(P->dtype, srcs, fold, P->k, tm, cm, dst, (size_t)P->c_cnt, 0, ls, fs,
+                                     sc->out_scale, sc->amax, st);
+    }
     return mvx_op_program(P->op, P->dtype, srcs, fold, P->k, tm, cm, dst, (size_t)P->c_cnt, st);
 }

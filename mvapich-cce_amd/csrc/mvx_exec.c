@@ -482,7 +482,7 @@ int mvxi_run_device_eager(mvx_comm_t *c, const job_t *J, hipStream_t st)
     c->ran_exch = MVX_EXCH_P2P;   /* unless a variant below takes the call */
     if (c->exch == MVX_EXCH_PIPE) return run_device_pipe(c, J, st);
     if (c->exch == MVX_EXCH_COLL && J->nr == 1 && J->t[0].alltoall && J->t[0].allgather &&
-        J->P[0].opkind == MVX_OPKIND_PREDEFINED && coll_regular(&J->P[0], &blk))
+        J->P[0].opkind == MVX_OPKIND_PREDEFINED && !mvxi_scaled(J->P[0].op) && coll_regular(&J->P[0], &blk))
         return run_device_coll(c, J, blk, st);
     return run_device_plain(c, J, st);
 }

@@ -328,6 +328,12 @@ typedef struct {           /* struct MPIR_OP, include/mpiops.h:1-11 */
     MVX_Device_function *dop;  /* stream-ordered device function */
     unsigned cookie;
     int commute, permanent;
+    /* a scaled sum (mvx_op_create_scaled_sum): no function; planned as a
+     * predefined commutative op, combined by MVX_SCALED_SUM's kernels */
+    int scaled, nranks;
+    float out_scale;
+    void *amax;                /* the caller's device word, or NULL */
+    float rank_scale[MVX_MAXP];
 } mvx_op_t;
 
 MVXI int mvxi_predefined(MPI_Op op);
@@ -336,6 +342,8 @@ static inline int mvxi_acc32(MPI_Op op) { return op == MVX_SUM_ACC32 || op == MV
 /* the ranks' mean MVX_AVG (predefined too): MPI_SUM's program divided once */
 static inline int mvxi_avg(MPI_Op op) { return op == MVX_AVG; }
 MVXI mvx_op_t *mvxi_user_op(MPI_Op op);
+/* the op's entry if it is a scaled sum, else NULL */
+MVXI const mvx_op_t *mvxi_scaled(MPI_Op op);
 MVXI int mvxi_op_kind(MPI_Op op);
 MVXI int mvxi_op_verdict(MPI_Op op, MPI_Datatype dt);
 MVXI MPI_Datatype mvxi_user_handle(MPI_Datatype dt);
@@ -350,14 +358,18 @@ MVXI int mvxi_wide_temps(const mvx_plan *P);
  * for leaves aligned like `like`: the leaves' own residue mod 16, or for f32
  * slots the one that puts the first whole word of narrow elements on a
  * 16-byte boundary of the floats (mvx_ops.hip: split, split_f32) */
-/* the plan's intermediates are f32 temporaries: the f32-accumulating ops, and
- * MVX_AVG on the narrow floats (its other types are 4 and 8 bytes) */
-static inline int mvxi_wide_f32(const mvx_plan *P) { return mvxi_acc32(P->op) || (mvxi_avg(P->op) && P->esize < 4); }
+/* the plan's intermediates are f32 temporaries: the f32-accumulating ops,
+ * MVX_AVG on the narrow floats (its other types are 4 and 8 bytes), and a
+ * scaled sum on every type it has (MPI_FLOAT's own format) */
+static inline int mvxi_wide_f32(const mvx_plan *P)
+{
+    return mvxi_acc32(P->op) || (mvxi_avg(P->op) && P->esize < 4) || mvxi_scaled(P->op) != NULL;
+}
 static inline size_t mvxi_wide_esize(const mvx_plan *P) { return mvxi_wide_f32(P) ? 4 : (size_t)P->esize; }
 static inline size_t mvxi_wide_residue(const mvx_plan *P, const void *like)
 {
     size_t head;
-    if (!mvxi_wide_f32(P)) return (uintptr_t)like & 15;
+    if (!mvxi_wide_f32(P) || P->esize == 4) return (uintptr_t)like & 15;
     head = ((4 - ((uintptr_t)like & 3)) & 3) / (size_t)P->esize;
     return (16 - 4 * head) & 15;
 }

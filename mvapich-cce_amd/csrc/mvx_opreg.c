@@ -22,6 +22,12 @@ mvx_op_t *mvxi_user_op(MPI_Op op)
     return &g_user_ops[i];
 }
 
+const mvx_op_t *mvxi_scaled(MPI_Op op)
+{
+    const mvx_op_t *o = mvxi_user_op(op);
+    return o && o->scaled ? o : NULL;
+}
+
 static int op_register(MPI_User_function *fn, MVX_Device_function *dfn, int commute, MPI_Op *op)
 {
     int i;
@@ -33,6 +39,7 @@ static int op_register(MPI_User_function *fn, MVX_Device_function *dfn, int comm
             g_user_ops[i].cookie = OP_COOKIE;
             g_user_ops[i].commute = commute;
             g_user_ops[i].permanent = 0;
+            g_user_ops[i].scaled = 0;
             *op = USER_OP_BASE + i;
             return MPI_SUCCESS;
         }
@@ -56,6 +63,23 @@ int mvx_op_create_device(MVX_Device_function *function, int commute, MPI_Op *op)
     return op_register(NULL, function, commute, op);
 }
 
+/* EXTENSION (mvx_coll.h): a handle of the user-op table that carries its own
+ * copy of the ranks' scales; MPI_Op_free frees it */
+int mvx_op_create_scaled_sum(const float *rank_scale, int nranks, float out_scale, void *amax_dev, MPI_Op *op)
+{
+    mvx_op_t *o;
+    int rc;
+    if (!rank_scale || nranks < 1 || nranks > MVX_MAXP || ((uintptr_t)amax_dev & 3)) return MPI_ERR_ARG;
+    if ((rc = op_register(NULL, NULL, 1, op))) return rc;
+    o = mvxi_user_op(*op);
+    o->scaled = 1;
+    o->nranks = nranks;
+    o->out_scale = out_scale;
+    o->amax = amax_dev;
+    memcpy(o->rank_scale, rank_scale, (size_t)nranks * sizeof *rank_scale);
+    return MPI_SUCCESS;
+}
+
 int MPI_Op_free(MPI_Op *op)  /* opfree.c:51-82 */
 {
     mvx_op_t *o;
@@ -76,7 +100,7 @@ int mvx_op_free(MPI_Op *op) { return MPI_Op_free(op); }
 int mvxi_op_kind(MPI_Op op)
 {
     const mvx_op_t *o = mvxi_predefined(op) ? NULL : mvxi_user_op(op);
-    if (!o) return MVX_OPKIND_PREDEFINED;
+    if (!o || o->scaled) return MVX_OPKIND_PREDEFINED;
     return o->commute ? MVX_OPKIND_USER_COMMUTE : MVX_OPKIND_USER_NONCOMMUTE;
 }
 
@@ -86,6 +110,7 @@ int mvxi_op_kind(MPI_Op op)
 int mvxi_op_verdict(MPI_Op op, MPI_Datatype dt)
 {
     if (mvxi_predefined(op)) return mvx_op_apply(op, dt, NULL, NULL, 0, NULL);
+    if (mvxi_scaled(op)) return mvx_op_apply(MVX_SCALED_SUM, dt, NULL, NULL, 0, NULL);
     return mvxi_user_op(op) ? MPI_SUCCESS : MPI_ERR_OP;
 }
 

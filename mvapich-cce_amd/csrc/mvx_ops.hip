@@ -5,7 +5,7 @@
 // never touch the device or a buffer; run() is the one place that launches.
 // mvx_op_plan answers with the plan alone.  The kernels are in mvx_ops_kern.h
 // (design notes at its top), their host-side tables in mvx_ops_tab.h and
-// mvx_ops_{cmp,arith,logic,loc,half,fp8,acc32,avg}.hip.
+// mvx_ops_{cmp,arith,logic,loc,half,fp8,acc32,avg,scaled}.hip.
 #include <stdlib.h>
 
 #include "mvx_dtype.h"
@@ -107,7 +107,8 @@ static int ekind(int dtype)
 // (global_ops.c:158-161 and every sibling default), and MPI_ERR_OP for a
 // handle outside MPI_MAX..MPI_MAXLOC that is not one of the extension
 // ops.  MVX_SUM_ACC32 and MVX_PROD_ACC32 have a case for the four
-// narrow floating types alone; MVX_AVG has those and the f32 / f64 kinds.
+// narrow floating types alone; MVX_AVG has those and the f32 / f64 kinds;
+// the device-layer index MVX_SCALED_SUM those four and the f32 kind.
 static bool acc32(int op) { return op == MVX_SUM_ACC32 || op == MVX_PROD_ACC32; }
 
 static const KSet *lookup(int op, int dtype, int *rc)
@@ -116,6 +117,7 @@ static const KSet *lookup(int op, int dtype, int *rc)
     *rc = MVX_ERR_OP_NOT_DEFINED;
     if (acc32(op)) return lookup_acc32(op, ek);
     if (op == MVX_AVG) return lookup_avg(ek);
+    if (op == MVX_SCALED_SUM) return lookup_scaled(ek);
     if (ek == EK_LOGICAL && (op == MPI_BAND || op == MPI_BOR || op == MPI_BXOR))
         ek = EK_U32;                 // bitwise on the MPI_Fint word
     if (ek == EK_F16 || ek == EK_BF16) {
@@ -301,10 +303,12 @@ static Plan plan_params(const KSet *ks, Params &P)
 
 static Plan g_last;        // the last launch (not thread-safe)
 
-static int run(const Plan &pl, const Params &P, hipStream_t stream)
+// (P and B are the scaled sum's parameter structs, which begin with every
+// other kernel's: a kernel takes as many bytes as its own argument has)
+static int run(const Plan &pl, const SParams &P, hipStream_t stream)
 {
-    BodyParams B;
-    void *args[] = {const_cast<Params *>(&P)};
+    SBodyParams B;
+    void *args[] = {const_cast<SParams *>(&P)};
     if (pl.body) {
         memset(&B, 0, sizeof B);
         for (int q = 0; q < P.k; ++q) B.src[q] = reinterpret_cast<const u32x4 *>(P.src[q]);
@@ -312,6 +316,7 @@ static int run(const Plan &pl, const Params &P, hipStream_t stream)
         B.nvec = P.nvec;
         B.k = P.k;
         B.divisor = P.divisor;
+        B.sc = P.sc;
         args[0] = &B;
     }
     hipError_t e = hipLaunchKernel(pl.fn, dim3(pl.blocks), dim3(256), args, pl.lds, stream);
@@ -319,11 +324,19 @@ static int run(const Plan &pl, const Params &P, hipStream_t stream)
     return e == hipSuccess ? MPI_SUCCESS : MPI_ERR_OTHER;
 }
 
+// MVX_SCALED_SUM through the entry points that take no scales: all of them 1, no amax
+static void unit_scales(SParams &P)
+{
+    for (int q = 0; q < MVX_COMBINE_KMAX; ++q) P.sc.lscale[q] = P.sc.fscale[q] = 1.0f;
+    P.sc.oscale = 1.0f;
+    P.sc.amax = nullptr;
+}
+
 // The argument checks of mvx_op_program, then P: MPI_SUCCESS (*ksp null for
 // n == 0: nothing to do) or the error code
 static int program_params(int op, int dtype, const void *const *srcs, const void *const *fold, int k,
                           unsigned tree_mask, unsigned chain_mask, const void *dst, size_t n,
-                          const KSet **ksp, Params &P)
+                          const KSet **ksp, SParams &P)
 {
     int rc;
     const KSet *ks = lookup(op, dtype, &rc);
@@ -347,6 +360,7 @@ static int program_params(int op, int dtype, const void *const *srcs, const void
     P.k = k;
     P.tree_mask = tree_mask;
     P.chain_mask = chain_mask;
+    unit_scales(P);
     /* the only programs over <= 2 leaves: nothing, or y0 op y1 */
     if (k == 2 && !(tree_mask & 1u) && !(chain_mask & 2u)) return MPI_ERR_ARG;
     *ksp = ks;
@@ -422,7 +436,7 @@ extern "C" int mvx_op_apply(int op, int dtype, const void *in, void *inout,
     const KSet *ks = lookup(op, dtype, &rc);
     if (!ks) return rc;
     if (n == 0) return MPI_SUCCESS;
-    Params P;
+    SParams P;
     memset(&P, 0, sizeof P);
     P.src[0] = (const char *)inout;   // a: the inout operand
     P.src[1] = (const char *)in;      // b
@@ -430,6 +444,7 @@ extern "C" int mvx_op_apply(int op, int dtype, const void *in, void *inout,
     P.n = (long)n;
     P.k = 2;
     P.divisor = 2;
+    unit_scales(P);
     return run(plan_params(ks, P), P, (hipStream_t)stream);
 }
 
@@ -438,10 +453,36 @@ extern "C" int mvx_op_program(int op, int dtype, const void *const *srcs,
                               unsigned chain_mask, void *dst, size_t n, void *stream)
 {
     const KSet *ks;
-    Params P;
+    SParams P;
     const int rc = program_params(op, dtype, srcs, fold, k, tree_mask, chain_mask, dst, n, &ks, P);
     if (rc != MPI_SUCCESS || !ks) return rc;
     return run(plan_params(ks, P), P, (hipStream_t)stream);
+}
+
+/* the checks on an f32 side's operands (P from program_params): f32 operands
+ * are floats, 4-byte aligned; f32 leaves are never folded */
+static int f32side_args(const Params &P, int side)
+{
+    for (int q = 0; q < P.k; ++q) {
+        if (side == MVX_F32_IN && (P.fold[q] || ((uintptr_t)P.src[q] & 3))) return MPI_ERR_ARG;
+    }
+    if (side == MVX_F32_OUT && ((uintptr_t)P.dst & 3)) return MPI_ERR_ARG;
+    return MPI_SUCCESS;
+}
+
+/* MVX_SCALED_SUM with the scales in P.sc.  MVX_F32_OUT: the leaves' scales and
+ * nothing else; MVX_F32_IN: the output scale and amax alone.  On MPI_FLOAT
+ * either side is the type itself, so the side only picks the scales. */
+static int run_scaled(const KSet *ks, SParams &P, int side, hipStream_t stream)
+{
+    if (side == MVX_F32_OUT) {
+        P.sc.oscale = 1.0f;
+        P.sc.amax = nullptr;
+    }
+    if (side == MVX_F32_IN)
+        for (int q = 0; q < MVX_COMBINE_KMAX; ++q) P.sc.lscale[q] = 1.0f;
+    if (side && ks->f32side[0].fn) return run(plan_f32(ks, P, side == MVX_F32_OUT, config()), P, stream);
+    return run(plan_params(ks, P), P, stream);
 }
 
 extern "C" int mvx_op_program_f32(int op, int dtype, const void *const *srcs, const void *const *fold, int k,
@@ -449,18 +490,40 @@ extern "C" int mvx_op_program_f32(int op, int dtype, const void *const *srcs, co
                                   void *stream)
 {
     const KSet *ks;
-    Params P;
+    SParams P;
     const int rc = program_params(op, dtype, srcs, fold, k, tree_mask, chain_mask, dst, n, &ks, P);
     if (rc != MPI_SUCCESS) return rc;
-    /* only the f32-accumulating ops have an f32 side */
-    if (!acc32(op) || (side != MVX_F32_OUT && side != MVX_F32_IN)) return MPI_ERR_ARG;
+    /* only the f32-accumulating ops (and the scaled sum, here with unit scales) have an f32 side */
+    if ((!acc32(op) && op != MVX_SCALED_SUM) || (side != MVX_F32_OUT && side != MVX_F32_IN)) return MPI_ERR_ARG;
     if (!ks) return MPI_SUCCESS;
-    /* f32 operands are floats: 4-byte aligned; f32 leaves are never folded */
-    for (int q = 0; q < k; ++q) {
-        if (side == MVX_F32_IN && (P.fold[q] || ((uintptr_t)P.src[q] & 3))) return MPI_ERR_ARG;
-    }
-    if (side == MVX_F32_OUT && ((uintptr_t)P.dst & 3)) return MPI_ERR_ARG;
+    if (f32side_args(P, side)) return MPI_ERR_ARG;
+    if (op == MVX_SCALED_SUM) return run_scaled(ks, P, side, (hipStream_t)stream);
     return run(plan_f32(ks, P, side == MVX_F32_OUT, config()), P, (hipStream_t)stream);
+}
+
+extern "C" int mvx_op_program_scaled(int dtype, const void *const *srcs, const void *const *fold, int k,
+                                     unsigned tree_mask, unsigned chain_mask, void *dst, size_t n, int side,
+                                     const float *leaf_scale, const float *fold_scale, float out_scale,
+                                     void *amax_dev, void *stream)
+{
+    const KSet *ks;
+    SParams P;
+    const int rc = program_params(MVX_SCALED_SUM, dtype, srcs, fold, k, tree_mask, chain_mask, dst, n, &ks, P);
+    if (rc != MPI_SUCCESS) return rc;
+    if ((side != 0 && side != MVX_F32_OUT && side != MVX_F32_IN) || !leaf_scale || ((uintptr_t)amax_dev & 3))
+        return MPI_ERR_ARG;
+    if (!ks) return MPI_SUCCESS;
+    if (f32side_args(P, side)) return MPI_ERR_ARG;
+    for (int q = 0; q < k; ++q) {
+        P.sc.lscale[q] = leaf_scale[q];
+        if (P.fold[q]) {
+            if (!fold_scale) return MPI_ERR_ARG;
+            P.sc.fscale[q] = fold_scale[q];
+        }
+    }
+    P.sc.oscale = out_scale;
+    P.sc.amax = (unsigned *)amax_dev;
+    return run_scaled(ks, P, side, (hipStream_t)stream);
 }
 
 extern "C" int mvx_op_program_avg(int dtype, const void *const *srcs, const void *const *fold, int k,
@@ -468,7 +531,7 @@ extern "C" int mvx_op_program_avg(int dtype, const void *const *srcs, const void
                                   int divisor, void *stream)
 {
     const KSet *ks;
-    Params P;
+    SParams P;
     int rc = program_params(MVX_AVG, dtype, srcs, fold, k, tree_mask, chain_mask, dst, n, &ks, P);
     if (rc != MPI_SUCCESS) return rc;
     if (divisor < 1 || (side != 0 && side != MVX_F32_IN)) return MPI_ERR_ARG;
@@ -489,7 +552,7 @@ extern "C" int mvx_op_plan(int op, int dtype, const void *const *srcs, const voi
                            struct mvx_launch_plan *out)
 {
     const KSet *ks;
-    Params P;
+    SParams P;
     const int rc = program_params(op, dtype, srcs, fold, k, tree_mask, chain_mask, dst, n, &ks, P);
     if (rc != MPI_SUCCESS) return rc;
     if (!out) return MPI_ERR_ARG;

@@ -3,7 +3,8 @@
 // chunks (what one lane moves per operand per step): element layouts, F<op, T>,
 // Chunk / CG, the chunk op CF with its SWAR, packed-16 and 8-bit float forms.
 // Last, the wide accumulator of the f32-accumulating ops (Wide, acc_steps,
-// acc_chunk) and MVX_AVG's finalising division (avg_fin, avg_chunk).  Device
+// acc_chunk), MVX_AVG's finalising division (avg_fin, avg_chunk) and the
+// scaled sum's scales and amax (Scl, scl_amax, wave_umax).  Device
 // code only; the kernels that use them are in
 // mvx_ops_kern.h (design notes there).
 #include <hip/hip_runtime.h>
@@ -21,8 +22,12 @@ enum { OMAX = 0, OMIN, OSUM, OPROD, OLAND, OBAND, OLOR, OBOR, OLXOR, OBXOR,
        OSUMA, OPRODA,
        // extension (MVX_AVG): the SUM program's value divided once by the rank
        // contributions it consumed (the end of this file)
-       OAVG };
-static_assert(OAVG == 14, "");
+       OAVG,
+       // extension (MVX_SCALED_SUM): the f32 SUM program over leaves multiplied
+       // by their ranks' scales, its value rescaled once, with a fused amax
+       // (the end of this file)
+       OSCL };
+static_assert(OAVG == 14 && OSCL == 15, "");
 
 // Element layouts: the reference's C types on x86-64 LP64.
 struct cf32 { float re, im; };                          // global_ops.c:43-46
@@ -575,13 +580,89 @@ template <typename T> struct narrow_float {
 };
 // the (op, type) pairs whose program runs on widened f32 values
 template <int O, typename T> struct acc_op {
-    static constexpr bool v = O == OSUMA || O == OPRODA || (O == OAVG && narrow_float<T>::v);
+    static constexpr bool v = O == OSUMA || O == OPRODA || (O == OAVG && narrow_float<T>::v) || O == OSCL;
 };
+
+// MVX_SCALED_SUM (OSCL), the per-rank scaled sum: the f32 program above with
+// accf = add, over leaves that are multiplied, right after they are widened,
+// by the scale of the rank they came from (one f32 multiply each, fold
+// partners by theirs); the program's value is multiplied once by oscale and
+// narrowed once.  Where the caller asked for it, the largest magnitude of the
+// values about to be narrowed is kept on the way: as the unsigned maximum of
+// bits(v) & 0x7fffffff, which orders magnitudes as floats do and puts every
+// NaN above infinity, so a NaN result leaves a NaN word.  A lane keeps its
+// maximum in a register over everything it stores; at the end of the kernel a
+// wave folds its 64 lanes with DPP row rotations and four v_readlane (no LDS:
+// the body kernels' reservation is their residency cap) and one lane issues a
+// single global_atomic_umax on the caller's word.  On float the leaves are
+// their own f32 values (Wide<float>), so the same program serves it: MPI_SUM's
+// per-step path cannot, the leaves change before the first step.
+struct Scl {
+    float lscale[8];      // per leaf: its rank's scale
+    float fscale[8];      // per fold partner
+    float oscale;         // the program's value, once
+    unsigned *amax;       // device word for max |v| before narrowing, or null
+};
+// the scales in an OSCL kernel's launch parameters (SParams, SBodyParams); a
+// template, so that the kernels written once for both parameter types name
+// them only where O == OSCL is instantiated
+template <int O, typename PT>
+__device__ __forceinline__ const Scl &scl_of(const PT &P) { return P.sc; }
+
+__device__ __forceinline__ uint32_t f32_bits(float f)
+{
+    uint32_t w;
+    __builtin_memcpy(&w, &f, 4);
+    return w;
+}
+
+template <int L>
+__device__ __forceinline__ unsigned scl_amax(unsigned m, const float (&y)[L])
+{
+#pragma unroll
+    for (int j = 0; j < L; ++j) {
+        const unsigned b = f32_bits(y[j]) & 0x7fffffffu;
+        m = b > m ? b : m;
+    }
+    return m;
+}
+
+// the maximum over the wave's 64 lanes, in every lane; all lanes active
+__device__ __forceinline__ unsigned wave_umax(unsigned m)
+{
+    unsigned t;
+    t = (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0x128, 0xF, 0xF, false); m = t > m ? t : m;   // row_ror:8
+    t = (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0x124, 0xF, 0xF, false); m = t > m ? t : m;   // row_ror:4
+    t = (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0x122, 0xF, 0xF, false); m = t > m ? t : m;   // row_ror:2
+    t = (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0x121, 0xF, 0xF, false); m = t > m ? t : m;   // row_ror:1
+    unsigned r = (unsigned)__builtin_amdgcn_readlane((int)m, 0);
+#pragma unroll
+    for (int row = 1; row < 4; ++row) {
+        t = (unsigned)__builtin_amdgcn_readlane((int)m, 16 * row);
+        r = t > r ? t : r;
+    }
+    return r;
+}
+
+// the end of a kernel whose lanes kept a maximum each: at most one atomic per
+// wave, and none from a wave whose maximum the word already holds.  The word
+// only grows while kernels run, so a stale read can only cost an atomic that
+// was not needed; without the read the 8 x 64 MiB tree's 32768 waves queued
+// on one address for 390 us against 95 us (tools/bench_kernels.py scaled).
+__device__ __forceinline__ void amax_commit(unsigned *amax, unsigned m)
+{
+    m = wave_umax(m);
+    if ((threadIdx.x & 63) == 0 && m > __hip_atomic_load(amax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+        atomicMax(amax, m);
+}
+
+// a lone unfolded leaf that no scale touches is copied, bits and all
+__device__ __forceinline__ bool scl_unit(const Scl &sc) { return sc.lscale[0] == 1.0f && sc.oscale == 1.0f; }
 
 template <int O>
 __device__ __forceinline__ float accf(float a, float b)
 {
-    static_assert(O == OSUMA || O == OPRODA || O == OAVG, "");
+    static_assert(O == OSUMA || O == OPRODA || O == OAVG || O == OSCL, "");
     return O == OPRODA ? a * b : a + b;
 }
 
@@ -633,6 +714,13 @@ template <> struct Wide<bf16> {
         __builtin_memcpy(&w, &h, 4);
         return w;
     }
+};
+
+// float (the scaled sum alone): a word is its own f32 value
+template <> struct Wide<float> {
+    static constexpr int L = 1;
+    static __device__ __forceinline__ void widen(uint32_t w, float (&y)[1]) { y[0] = bits_f32(w); }
+    static __device__ __forceinline__ uint32_t narrow(const float (&y)[1]) { return f32_bits(y[0]); }
 };
 
 // f16: v_cvt_f32_f16 widens exactly (subnormals included); the pair of a
@@ -744,6 +832,63 @@ __device__ __forceinline__ void acc_chunk(Chunk<T> (&x)[KMAX], const Chunk<T> (&
         for (int j = 0; j < L; ++j) y[0][j] = avg_fin<O>(y[0][j], divisor);
         x[0].w[w] = Wide<T>::narrow(y[0]);
     }
+}
+
+template <typename T>
+__device__ __forceinline__ uint32_t chunk_word(const Chunk<T> &x, int w)
+{
+    if constexpr (std::is_same<T, float>::value) return f32_bits(x.e[w]);
+    else return x.w[w];
+}
+
+// OSCL's acc_chunk: the leaves scaled as they are widened, the value rescaled
+// once; returns the chunk's amax where sc.amax asks for one (else 0).  On float
+// a word is an element (Wide<float>).
+template <typename T, int KMAX, int PROG>
+__device__ __forceinline__ unsigned scl_chunk(Chunk<T> (&x)[KMAX], const Chunk<T> (&xf)[KMAX], unsigned fold_mask,
+                                              int k, unsigned tree_mask, unsigned chain_mask, const Scl &sc)
+{
+    constexpr int L = Wide<T>::L;
+    unsigned am = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        float y[KMAX][L];
+#pragma unroll
+        for (int q = 0; q < KMAX; ++q) {
+            if (PROG == 1 || q < k) {
+                Wide<T>::widen(chunk_word(x[q], w), y[q]);
+#pragma unroll
+                for (int j = 0; j < L; ++j) y[q][j] *= sc.lscale[q];
+                if (PROG == 0 && (fold_mask & (1u << q))) {
+                    float f[L];
+                    Wide<T>::widen(chunk_word(xf[q], w), f);
+#pragma unroll
+                    for (int j = 0; j < L; ++j) y[q][j] = accf<OSCL>(y[q][j], f[j] * sc.fscale[q]);
+                }
+            }
+        }
+        acc_steps<OSCL, KMAX, L, PROG>(y, k, tree_mask, chain_mask);
+#pragma unroll
+        for (int j = 0; j < L; ++j) y[0][j] *= sc.oscale;
+        if (sc.amax) am = scl_amax(am, y[0]);
+        if constexpr (std::is_same<T, float>::value) x[0].e[w] = y[0][0];
+        else x[0].w[w] = Wide<T>::narrow(y[0]);
+    }
+    return am;
+}
+
+// OSCL's lone leaf that is copied: the amax of the chunk's widened elements
+template <typename T>
+__device__ __forceinline__ unsigned amax_chunk(const Chunk<T> &x)
+{
+    unsigned am = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        float y[Wide<T>::L];
+        Wide<T>::widen(chunk_word(x, w), y);
+        am = scl_amax(am, y);
+    }
+    return am;
 }
 
 // OAVG on float and double: the finalising step on every element of the

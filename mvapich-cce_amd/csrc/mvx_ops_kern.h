@@ -3,7 +3,7 @@
 // path and what they take (Params, BodyParams), written for gfx950 (CDNA4,
 // wave64).  The ops on elements and chunks are in mvx_ops_fn.h; the host-side
 // tables that name every instantiation are in mvx_ops_tab.h, which mvx_ops.hip
-// and the per-op table units mvx_ops_{cmp,arith,logic,loc,half,fp8,acc32,avg}.hip include.
+// and the per-op table units mvx_ops_{cmp,arith,logic,loc,half,fp8,acc32,avg,scaled}.hip include.
 // Built into libmvx_hip.so; C-ABI in include/mvx_hip.h.
 //
 // One kernel template covers every predefined op x type of the reference
@@ -50,6 +50,10 @@ struct Params {
     unsigned chain_mask;  // bit q (q >= 1): y[0] = op(y[0], y[q]) after the tree
     int divisor;          // OAVG alone reads it: the rank contributions of the whole program
 };
+// the scaled sum's kernels: the same, with its scales and amax word behind
+struct SParams : Params {
+    Scl sc;
+};
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));  // one dwordx4
 
@@ -77,50 +81,6 @@ __device__ __forceinline__ void reduce_leaves(T (&y)[KMAX], int k, unsigned tree
 #pragma unroll
         for (int q = 1; q < KMAX; ++q)
             if (chain_mask & (1u << q)) y[0] = F<O, T>::f(y[0], y[q]);
-    }
-}
-
-// the same element of every leaf through the f32-accumulating program
-// (acc_op): widened, folded and combined in f32, narrowed once.  A single
-// unfolded leaf has no step: it is copied, bits and all (a NaN's payload
-// would not survive the way to f32 and back), as the per-step ops copy it
-// (OAVG: unless it is to be divided).
-template <int O, typename T, int KMAX>
-__device__ __forceinline__ void scalar_elem_acc(const Params &P, long i)
-{
-    if (P.k == 1 && !P.fold[0] && (O != OAVG || P.divisor == 1)) {
-        store_elt(reinterpret_cast<T *>(P.dst) + i, reinterpret_cast<const T *>(P.src[0])[i]);
-        return;
-    }
-    float y[KMAX][1];
-#pragma unroll
-    for (int q = 0; q < KMAX; ++q) {
-        if (q < P.k) {
-            y[q][0] = widen_elt(reinterpret_cast<const T *>(P.src[q]) + i);
-            if (P.fold[q]) y[q][0] = accf<O>(y[q][0], widen_elt(reinterpret_cast<const T *>(P.fold[q]) + i));
-        }
-    }
-    acc_steps<O, KMAX, 1, 0>(y, P.k, P.tree_mask, P.chain_mask);
-    narrow_elt(reinterpret_cast<T *>(P.dst) + i, avg_fin<O>(y[0][0], P.divisor));
-}
-
-template <int O, typename T, int KMAX>
-__device__ __forceinline__ void scalar_elem(const Params &P, long i)
-{
-    if constexpr (acc_op<O, T>::v) {
-        scalar_elem_acc<O, T, KMAX>(P, i);
-    } else {
-        T y[KMAX];
-#pragma unroll
-        for (int q = 0; q < KMAX; ++q) {
-            if (q < P.k) {
-                y[q] = reinterpret_cast<const T *>(P.src[q])[i];
-                if (P.fold[q]) y[q] = F<O, T>::f(y[q], reinterpret_cast<const T *>(P.fold[q])[i]);
-            }
-        }
-        reduce_leaves<O, T, KMAX>(y, P.k, P.tree_mask, P.chain_mask);
-        if constexpr (O == OAVG) y[0] = avg_fin<O>(y[0], P.divisor);
-        store_elt(reinterpret_cast<T *>(P.dst) + i, y[0]);
     }
 }
 
@@ -200,125 +160,44 @@ __device__ __forceinline__ void batch_acc(Chunk<T> (&x)[U][KMAX], const u32x4 *(
     for (int u = 0; u < U; ++u) acc_chunk<O, T, KMAX, PROG>(x[u], xf[u], fmask, k, tree_mask, chain_mask, divisor);
 }
 
-// PROG = 0: the program comes from the masks (any chain of trees over
-// k <= KMAX leaves); PROG = 1: the full balanced tree over exactly KMAX
-// leaves, steps fixed at compile time -- the Allreduce / Reduce order at
-// p = 4 and 8 (Rabenseifner), where the generic form evaluated and
-// discarded 24 masked steps for the 7 the tree needs.
-template <int O, typename T, int KMAX, int U, int NT, int PROG = 0>
-__global__ void __launch_bounds__(256)
-k_combine(const Params P)
+// OSCL's batch_acc, through scl_chunk: the amax of the chunks inside the body
+// goes into am (chunks past the end are computed on unloaded registers, and
+// count for nothing).
+template <typename T, int KMAX, int U, int NT, int PROG>
+__device__ __forceinline__ void batch_scl(Chunk<T> (&x)[U][KMAX], const u32x4 *(&fold)[KMAX], long c0,
+                                          long nvec, int k, unsigned tree_mask, unsigned chain_mask,
+                                          const Scl &sc, unsigned &am)
 {
-    // the launch may reserve dynamic LDS to cap resident blocks per CU
-    // (plan(), Config::cap_*); the kernel never uses it -- the reference here
-    // (never taken) marks the kernel as one that takes dynamic LDS
-    extern __shared__ char lds_cap[];
-    if (P.n < 0) lds_cap[threadIdx.x] = 0;
-    constexpr int V = CG<T>::v;
-    const long tid = (long)blockIdx.x * 256 + threadIdx.x;
-    const long nthr = (long)gridDim.x * 256;
-
-    if (!P.vec_ok) {  // operands misaligned against each other: element loads
-        for (long i = tid; i < P.n; i += nthr) scalar_elem<O, T, KMAX>(P, i);
+    Chunk<T> xf[U][KMAX];
+    unsigned fmask = 0;
+    if constexpr (PROG == 0) {
+#pragma unroll
+        for (int q = 0; q < KMAX; ++q) {
+            if (q < k && fold[q]) {
+                fmask |= 1u << q;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const long c = c0 + (long)u * 256;
+                    if (c < nvec) xf[u][q] = ld_chunk<T, NT>(fold[q], c);
+                }
+            }
+        }
+    }
+    // a lone leaf that no scale touches is copied as it is (scalar_elem_scl); it still counts for amax
+    if (PROG == 0 && k == 1 && !fmask && scl_unit(sc)) {
+        if (sc.amax) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const unsigned m = amax_chunk(x[u][0]);
+                if (c0 + (long)u * 256 < nvec) am = m > am ? m : am;
+            }
+        }
         return;
     }
-    {   // head and tail elements outside the aligned body
-        const long tail0 = P.head + P.nvec * V;
-        const long nscal = P.head + (P.n - tail0);
-        for (long s = tid; s < nscal; s += nthr) {
-            const long i = s < P.head ? s : tail0 + (s - P.head);
-            scalar_elem<O, T, KMAX>(P, i);
-        }
-    }
-    const u32x4 *src[KMAX];
-    const u32x4 *fold[KMAX];
 #pragma unroll
-    for (int q = 0; q < KMAX; ++q) {
-        src[q] = reinterpret_cast<const u32x4 *>(P.src[q] + P.head * (long)sizeof(T));
-        fold[q] = P.fold[q] ? reinterpret_cast<const u32x4 *>(P.fold[q] + P.head * (long)sizeof(T)) : nullptr;
-    }
-    u32x4 *dst = reinterpret_cast<u32x4 *>(P.dst + P.head * (long)sizeof(T));
-    const int k = P.k;
-    const unsigned tmask = P.tree_mask, cmask = P.chain_mask;
-
-    for (long c0 = (long)blockIdx.x * (256 * U) + threadIdx.x; c0 < P.nvec; c0 += nthr * U) {
-        Chunk<T> x[U][KMAX];
-        // issue every load of the iteration before the first use
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const long c = c0 + (long)u * 256;
-            if (c < P.nvec) {
-#pragma unroll
-                for (int q = 0; q < KMAX; ++q)
-                    if (PROG == 1 || q < k) x[u][q] = ld_chunk<T, NT>(src[q], c);
-            }
-        }
-        if constexpr (acc_op<O, T>::v) {
-            batch_acc<O, T, KMAX, U, NT, PROG>(x, fold, c0, P.nvec, k, tmask, cmask, P.divisor);
-        } else {
-#pragma unroll
-            for (int q = 0; q < KMAX; ++q) {
-                // fixed trees are launched without folded leaves (mvx_op_program):
-                // no branch between the loads and the tree keeps every load of
-                // the iteration in flight before the first add
-                if (PROG == 0 && q < k && fold[q]) {
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        const long c = c0 + (long)u * 256;
-                        if (c < P.nvec) {
-                            const Chunk<T> f = ld_chunk<T, NT>(fold[q], c);
-                            CF<O, T>::f(x[u][q], f);
-                        }
-                    }
-                }
-            }
-            // the combine program: each wave-uniform step is tested once and
-            // applied to all U*V elements of the batch (chunks past the end
-            // compute on unloaded registers and are never stored)
-            if constexpr (KMAX == 2) {
-                if (k == 2) {
-#pragma unroll
-                    for (int u = 0; u < U; ++u)
-                        CF<O, T>::f(x[u][0], x[u][1]);
-                }
-            } else if constexpr (PROG == 1) {
-#pragma unroll
-                for (int h = 1; h < KMAX; h <<= 1)
-#pragma unroll
-                    for (int q = 0; q + h < KMAX; q += 2 * h)
-#pragma unroll
-                        for (int u = 0; u < U; ++u)
-                            CF<O, T>::f(x[u][q], x[u][q + h]);
-            } else {
-#pragma unroll
-                for (int l = 0; (1 << l) < KMAX; ++l) {
-#pragma unroll
-                    for (int q = 0; q + (1 << l) < KMAX; ++q) {
-                        if (tmask & (1u << (l * 8 + q))) {
-#pragma unroll
-                            for (int u = 0; u < U; ++u)
-                                CF<O, T>::f(x[u][q], x[u][q + (1 << l)]);
-                        }
-                    }
-                }
-#pragma unroll
-                for (int q = 1; q < KMAX; ++q) {
-                    if (cmask & (1u << q)) {
-#pragma unroll
-                        for (int u = 0; u < U; ++u)
-                            CF<O, T>::f(x[u][0], x[u][q]);
-                    }
-                }
-            }
-            // OAVG: the program's value divided once
-#pragma unroll
-            for (int u = 0; u < U; ++u) avg_chunk<O, T>(x[u][0], P.divisor);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const long c = c0 + (long)u * 256;
-            if (c < P.nvec) st_chunk<T, NT>(dst, c, x[u][0]);
-        }
+    for (int u = 0; u < U; ++u) {
+        const unsigned m = scl_chunk<T, KMAX, PROG>(x[u], xf[u], fmask, k, tree_mask, chain_mask, sc);
+        if (c0 + (long)u * 256 < nvec) am = m > am ? m : am;
     }
 }
 
@@ -336,6 +215,9 @@ struct BodyParams {
     int k;       // leaves (k_chain_body<..., 8, ...>: 5 to 8)
     int divisor; // Params::divisor
 };
+struct SBodyParams : BodyParams {
+    Scl sc;      // SParams::sc (no leaf of a body launch is folded: fscale is not read)
+};
 
 // 56 KiB of static LDS per block: 2 resident blocks (8 waves) per CU.
 // tools/tune_occ.hip, profiles/r02/tune_occ_lds.jsonl: the 8-leaf f32 tree
@@ -349,92 +231,6 @@ struct BodyParams {
 #define BODY_ST_NT 1   // non-temporal result stores (cached: C4 204.8 -> 215.0 us, C5 96.1 -> 97.1, C3 unchanged)
 #endif
 
-template <int O, typename T, int KMAX, int U>
-__global__ void __launch_bounds__(256)
-k_tree_body(const BodyParams P)
-{
-    __shared__ char lds_cap[BODY_LDS_CAP];
-    if (P.nvec < 0) lds_cap[threadIdx.x] = 0;
-    const long nthr = (long)gridDim.x * 256;
-    for (long c0 = (long)blockIdx.x * (256 * U) + threadIdx.x; c0 < P.nvec; c0 += nthr * U) {
-        Chunk<T> x[U][KMAX];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const long c = c0 + (long)u * 256;
-            if (c < P.nvec)
-#pragma unroll
-                for (int q = 0; q < KMAX; ++q) x[u][q] = ld_chunk<T, 1>(P.src[q], c);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const long c = c0 + (long)u * 256;
-            if (c < P.nvec) {
-                if constexpr (acc_op<O, T>::v) {
-                    acc_chunk<O, T, KMAX, 1>(x[u], x[u], 0u, KMAX, 0u, 0u, P.divisor);
-                } else {
-#pragma unroll
-                    for (int h = 1; h < KMAX; h <<= 1)
-#pragma unroll
-                        for (int q = 0; q + h < KMAX; q += 2 * h)
-                            CF<O, T>::f(x[u][q], x[u][q + h]);
-                    avg_chunk<O, T>(x[u][0], P.divisor);
-                }
-                st_chunk<T, BODY_ST_NT>(P.dst, c, x[u][0]);
-            }
-        }
-    }
-}
-
-// The same over a full CHAIN ((y0 op y1) op y2) ..., the pairwise
-// Reduce_scatter's order (C4: k = 4, p = 4).  The 8-leaf instantiation
-// takes chains of 5 to 8 leaves (P.k, a wave-uniform test per leaf): the
-// pairwise chains at p = 5, 6, 7, which otherwise run the masked program at
-// one chunk per lane.
-template <int O, typename T, int KMAX, int U>
-__global__ void __launch_bounds__(256)
-k_chain_body(const BodyParams P)
-{
-    __shared__ char lds_cap[BODY_LDS_CAP];
-    if (P.nvec < 0) lds_cap[threadIdx.x] = 0;
-    const int k = KMAX == 8 ? P.k : KMAX;
-    const long nthr = (long)gridDim.x * 256;
-    for (long c0 = (long)blockIdx.x * (256 * U) + threadIdx.x; c0 < P.nvec; c0 += nthr * U) {
-        Chunk<T> x[U][KMAX];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const long c = c0 + (long)u * 256;
-            if (c < P.nvec)
-#pragma unroll
-                for (int q = 0; q < KMAX; ++q)
-                    if (q < k) x[u][q] = ld_chunk<T, 1>(P.src[q], c);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const long c = c0 + (long)u * 256;
-            if (c < P.nvec) {
-                if constexpr (acc_op<O, T>::v) {
-                    acc_chunk<O, T, KMAX, 0>(x[u], x[u], 0u, k, 0u, (1u << k) - 2u, P.divisor);
-                } else {
-#pragma unroll
-                    for (int q = 1; q < KMAX; ++q)
-                        if (q < k) CF<O, T>::f(x[u][0], x[u][q]);
-                    avg_chunk<O, T>(x[u][0], P.divisor);
-                }
-                st_chunk<T, BODY_ST_NT>(P.dst, c, x[u][0]);
-            }
-        }
-    }
-}
-
-// The masked program of an f32-accumulating op with one side in f32: what a
-// program over more than 8 leaves is cut into (mvx_combine.c), its
-// intermediates being f32 temporaries.  DIR = 0: narrow leaves (folds
-// allowed), f32 result, not narrowed; DIR = 1: f32 leaves, the result narrowed
-// once (OAVG, the last launch of such a program: divided, then narrowed).  A lane takes one 32-bit word of each narrow operand against L floats
-// of each f32 one (a dwordx4 for the 8-bit types, a dwordx2 for the 16-bit
-// ones).  Params: head elements lead to nvec such words where the narrow
-// side is 4-byte and the f32 side 4 * L-byte aligned (vec_ok), else every
-// element goes alone.
 template <typename T, int DIR>
 __device__ __forceinline__ float ld_f32side(const char *p, long i)
 {
@@ -442,71 +238,26 @@ __device__ __forceinline__ float ld_f32side(const char *p, long i)
     else return reinterpret_cast<const float *>(p)[i];
 }
 
-template <int O, typename T, int DIR>
-__global__ void __launch_bounds__(256)
-k_combine_f32(const Params P)
-{
-    constexpr int L = Wide<T>::L;
-    constexpr int KMAX = MVX_COMBINE_KMAX;
-    typedef float fL __attribute__((ext_vector_type(L)));
-    const long tid = (long)blockIdx.x * 256 + threadIdx.x;
-    const long nthr = (long)gridDim.x * 256;
-    const int k = P.k;
-    const unsigned tmask = P.tree_mask, cmask = P.chain_mask;
-    {   // every element (operands misaligned), or the head and the tail
-        const long tail0 = P.vec_ok ? P.head + P.nvec * L : 0;
-        const long nscal = P.vec_ok ? P.head + (P.n - tail0) : P.n;
-        for (long s = tid; s < nscal; s += nthr) {
-            const long i = !P.vec_ok || s < P.head ? s : tail0 + (s - P.head);
-            float y[KMAX][1];
-#pragma unroll
-            for (int q = 0; q < KMAX; ++q) {
-                if (q < k) {
-                    y[q][0] = ld_f32side<T, DIR>(P.src[q], i);
-                    if (DIR == 0 && P.fold[q]) y[q][0] = accf<O>(y[q][0], ld_f32side<T, 0>(P.fold[q], i));
-                }
-            }
-            acc_steps<O, KMAX, 1, 0>(y, k, tmask, cmask);
-            y[0][0] = avg_fin<O>(y[0][0], P.divisor);
-            if constexpr (DIR == 0) reinterpret_cast<float *>(P.dst)[i] = y[0][0];
-            else narrow_elt(reinterpret_cast<T *>(P.dst) + i, y[0][0]);
-        }
-        if (!P.vec_ok) return;
-    }
-    const long nb = P.head * (long)sizeof(T), fb = P.head * 4;   // the body's byte offset on either side
-    for (long c = tid; c < P.nvec; c += nthr) {
-        float y[KMAX][L];
-#pragma unroll
-        for (int q = 0; q < KMAX; ++q) {
-            if (q < k) {
-                if constexpr (DIR == 0) {
-                    Wide<T>::widen(reinterpret_cast<const uint32_t *>(P.src[q] + nb)[c], y[q]);
-                    if (P.fold[q]) {
-                        float f[L];
-                        Wide<T>::widen(reinterpret_cast<const uint32_t *>(P.fold[q] + nb)[c], f);
-#pragma unroll
-                        for (int j = 0; j < L; ++j) y[q][j] = accf<O>(y[q][j], f[j]);
-                    }
-                } else {
-                    const fL v = reinterpret_cast<const fL *>(P.src[q] + fb)[c];
-#pragma unroll
-                    for (int j = 0; j < L; ++j) y[q][j] = v[j];
-                }
-            }
-        }
-        acc_steps<O, KMAX, L, 0>(y, k, tmask, cmask);
-#pragma unroll
-        for (int j = 0; j < L; ++j) y[0][j] = avg_fin<O>(y[0][j], P.divisor);
-        if constexpr (DIR == 0) {
-            fL v;
-#pragma unroll
-            for (int j = 0; j < L; ++j) v[j] = y[0][j];
-            reinterpret_cast<fL *>(P.dst + fb)[c] = v;
-        } else {
-            reinterpret_cast<uint32_t *>(P.dst + nb)[c] = Wide<T>::narrow(y[0]);
-        }
-    }
-}
+// ---------------------------------------------------------------------------
+// The kernels that take Params / BodyParams are defined in mvx_ops_kern_def.h,
+// which is read twice: once for every op there was (MVX_KP = Params), once
+// more for the scaled sum, whose kernels take the same structs with its
+// scales behind (SParams, SBodyParams) as overloads of the same templates.
+// A field added to Params itself moves the hidden arguments behind it into
+// another cache line of the kernarg segment, which every launch of every
+// kernel then fetches (0.3 us a launch on the 256 MiB MPI_SUM); and a body
+// function shared by two thin kernels compiles to other code than the kernel
+// did.  Read twice, the existing kernels stay what they were, byte for byte.
+#define MVX_KP Params
+#define MVX_KBP BodyParams
+#include "mvx_ops_kern_def.h"
+#undef MVX_KP
+#undef MVX_KBP
+#define MVX_KP SParams
+#define MVX_KBP SBodyParams
+#include "mvx_ops_kern_def.h"
+#undef MVX_KP
+#undef MVX_KBP
 
 // MPI_LONG_DOUBLE_INT MAXLOC / MINLOC (global_ops.c:1365-1378 / 1605-1618)
 // as lane PAIRS.  An element is 32 bytes: the x87 value in the first 16

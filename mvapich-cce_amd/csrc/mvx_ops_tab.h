@@ -3,7 +3,7 @@
 // (Config), the descriptor of one kernel instantiation (KVar), the families
 // and sets built from them, the element kinds and the per-op table units'
 // lookup functions.  Included by mvx_ops.hip (dispatch and launch policy) and
-// by mvx_ops_{cmp,arith,logic,loc,half,fp8,acc32,avg}.hip, which instantiate the kernels of
+// by mvx_ops_{cmp,arith,logic,loc,half,fp8,acc32,avg,scaled}.hip, which instantiate the kernels of
 // mvx_ops_kern.h through the macros below, one translation unit each so that
 // they compile in parallel.
 #include <stdio.h>
@@ -114,10 +114,15 @@ struct KSet {
     const char *name;
 };
 
+// the overload of a kernel template that op O launches: the scaled sum's takes
+// SParams / SBodyParams (mvx_ops_kern.h)
+template <int O> using KFn = void (*)(const std::conditional_t<O == OSCL, SParams, Params>);
+template <int O> using KBodyFn = void (*)(const std::conditional_t<O == OSCL, SBodyParams, BodyParams>);
+
 template <int O, typename T, int KMAX, int U, int NT, int PROG>
 static KVar kvar_combine()
 {
-    return {(const void *)&k_combine<O, T, KMAX, U, NT, PROG>, &ksym<K_COMBINE, O, T, KMAX, U, NT, PROG>,
+    return {(const void *)static_cast<KFn<O>>(&k_combine<O, T, KMAX, U, NT, PROG>), &ksym<K_COMBINE, O, T, KMAX, U, NT, PROG>,
             U, false, 1, 0, 1, KMAX};
 }
 
@@ -137,7 +142,7 @@ static KFam kfam(int fam)
     f.var[V_NT] = kvar_combine<O, T, KMAX, U1, 1, PROG>();
     f.fam = (fam == FAM_TREE && alu_heavy<T>::v) ? FAM_PROG : fam;
     if constexpr (PROG == 1 && !alu_heavy<T>::v) {
-        f.var[V_BODY] = {(const void *)&k_tree_body<O, T, KMAX, U1>, &ksym<K_TREE_BODY, O, T, KMAX, U1>,
+        f.var[V_BODY] = {(const void *)static_cast<KBodyFn<O>>(&k_tree_body<O, T, KMAX, U1>), &ksym<K_TREE_BODY, O, T, KMAX, U1>,
                          U1, true, 1, 0, KMAX, KMAX};
     } else if constexpr (PROG == 1 && std::is_same<T, pxi>::value && (O == OMAXLOC || O == OMINLOC)) {
         const Config &c = config();
@@ -154,7 +159,7 @@ static KFam kchain()
 {
     KFam f = kfam<O, T, MVX_COMBINE_KMAX, 1, 1, 0>(FAM_PROG);
     if constexpr (!alu_heavy<T>::v) {
-        f.var[V_BODY] = {(const void *)&k_chain_body<O, T, KMAX, 2>, &ksym<K_CHAIN_BODY, O, T, KMAX, 2>,
+        f.var[V_BODY] = {(const void *)static_cast<KBodyFn<O>>(&k_chain_body<O, T, KMAX, 2>), &ksym<K_CHAIN_BODY, O, T, KMAX, 2>,
                          2, true, 1, 0, KMAX == 8 ? 5 : KMAX, KMAX};
     }
     return f;
@@ -207,11 +212,12 @@ static KSet kset(const char *name)
         s.prog2 = {};
     }
     s.f32side[0] = s.f32side[1] = KVar{};
-    if constexpr (acc_op<O, T>::v) {
+    // (the scaled sum on float has no other format to go through: its f32 sides are its own kernels)
+    if constexpr (acc_op<O, T>::v && narrow_float<T>::v) {
         // (MVX_AVG's launches before the last are MVX_SUM_ACC32's: it has the f32-leaves form alone)
         if constexpr (O != OAVG)
-            s.f32side[0] = {(const void *)&k_combine_f32<O, T, 0>, &ksym<K_COMBINE_F32, O, T, 0>, 1, false, 1, 0, 1, MVX_COMBINE_KMAX};
-        s.f32side[1] = {(const void *)&k_combine_f32<O, T, 1>, &ksym<K_COMBINE_F32, O, T, 1>, 1, false, 1, 0, 1, MVX_COMBINE_KMAX};
+            s.f32side[0] = {(const void *)static_cast<KFn<O>>(&k_combine_f32<O, T, 0>), &ksym<K_COMBINE_F32, O, T, 0>, 1, false, 1, 0, 1, MVX_COMBINE_KMAX};
+        s.f32side[1] = {(const void *)static_cast<KFn<O>>(&k_combine_f32<O, T, 1>), &ksym<K_COMBINE_F32, O, T, 1>, 1, false, 1, 0, 1, MVX_COMBINE_KMAX};
     }
     s.esize = (int)sizeof(T);
     s.chunk = CG<T>::bytes;
@@ -290,5 +296,6 @@ const KSet *lookup_half(int op, int ek);    // every op on the 16-bit floats  mv
 const KSet *lookup_fp8(int op, int ek);     // every op on the 8-bit floats   mvx_ops_fp8.hip
 const KSet *lookup_acc32(int op, int ek);   // MVX_SUM_ACC32, MVX_PROD_ACC32  mvx_ops_acc32.hip
 const KSet *lookup_avg(int ek);             // MVX_AVG                        mvx_ops_avg.hip
+const KSet *lookup_scaled(int ek);          // MVX_SCALED_SUM                 mvx_ops_scaled.hip
 
 }  // namespace mvx

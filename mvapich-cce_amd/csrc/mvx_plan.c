@@ -35,6 +35,7 @@
 #include <string.h>
 #include "mvx_coll.h"
 #include "mvx_hip.h"
+#include "mvx_internal.h"   /* mvxi_scaled */
 
 /* coll_table, intra_fns_new.c:129-132, flattened: the reference reads
  * row[-1] (the previous row's last entry) when p = 1. */
@@ -169,6 +170,8 @@ static int is_ieee(int t)
 static int op_symmetric(int op, int dtype)
 {
     int old = dtype, cnt = 1;
+    /* a scaled sum (a handle of the user-op table): f32 adds of scaled leaves, where it is defined */
+    if (mvxi_scaled(op)) return mvx_op_supported(MVX_SCALED_SUM, dtype);
     /* an undefined pair leaves every inout operand as it is (global_ops.c's
      * default branches): the result is the inout leaf's, so roles matter */
     if (!mvx_op_supported(op, dtype)) return 0;

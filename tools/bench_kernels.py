@@ -18,7 +18,8 @@ Modes (arguments): sweep, all, all-tree, ks, x87 add lines to the four
 configs; half runs only the 16-bit floating types against MPI_SHORT, fp8 only
 the 8-bit ones against MPI_UNSIGNED_CHAR, acc32 only MVX_SUM_ACC32 /
 MVX_PROD_ACC32 against MPI_SUM / MPI_PROD on the four narrow floating types,
-avg only MVX_AVG's 8-leaf tree against its sum twin (f32, E4M3).
+avg only MVX_AVG's 8-leaf tree against its sum twin (f32, E4M3), scaled only
+the scaled sum's tree and apply, with and without amax, against its twin.
 """
 import importlib
 import json
@@ -32,7 +33,8 @@ MIB = 1 << 20
 PEAK = 8000.0
 
 
-def run(mvx, name, op, dtype, k, shape, leaf_bytes, sets, reps=20, warm=3, quiet=False):
+def run(mvx, name, op, dtype, k, shape, leaf_bytes, sets, reps=20, warm=3, quiet=False, amax=None):
+    """amax: a device word; the launch then goes through op_program_scaled (scales 0.5, out_scale 2)."""
     import torch
     n_elems = leaf_bytes // mvx.dtype_info(dtype)[0]
     bufs = []
@@ -58,7 +60,11 @@ def run(mvx, name, op, dtype, k, shape, leaf_bytes, sets, reps=20, warm=3, quiet
 
     def launch(i):
         leaves, dst = bufs[i % sets]
-        if k == 2 and shape == 1:
+        if amax is not None:
+            hip = mvx.hip()
+            rc = mvx.op_program_scaled(dtype, leaves[:k], leaves[0] if k == 2 and shape == 1 else dst, n_elems,
+                                       hip.mvx_tree_mask(k), 0, [0.5] * k, 2.0, amax, stream=stream)
+        elif k == 2 and shape == 1:
             rc = mvx.op_apply(op, dtype, leaves[1], leaves[0], n_elems, stream)
         else:
             rc = mvx.op_combine(op, dtype, leaves, dst, n_elems, shape=shape, stream=stream)
@@ -150,8 +156,27 @@ def avg(mvx):
                 run(mvx, "M8-%s-%s-%d" % (kind, tn, rep), op, t, 8, 0, 64 * MIB, 2, reps=10, warm=2)
 
 
+def scaled(mvx):
+    """The scaled sum next to the sum it extends: the 8-leaf tree and the
+    apply at 64 MiB leaves on E4M3, BF16 and f32; unit scales without amax,
+    then real scales with amax; each triple three times over, twin first."""
+    import torch
+    word = torch.zeros(1, dtype=torch.int32, device="cuda")
+    for rep in range(3):
+        for t, tn, twin in ((72, "e4m3", mvx.MVX_SUM_ACC32), (65, "bf16", mvx.MVX_SUM_ACC32),
+                            (mvx.MPI_FLOAT, "f32", mvx.MPI_SUM)):
+            for k, shape, kn in ((8, 0, "tree8"), (2, 1, "apply")):
+                run(mvx, "S-%s-sum-%s-%d" % (kn, tn, rep), twin, t, k, shape, 64 * MIB, 2, reps=10, warm=2)
+                run(mvx, "S-%s-scaled-%s-%d" % (kn, tn, rep), mvx.MVX_SCALED_SUM, t, k, shape, 64 * MIB, 2, reps=10, warm=2)
+                run(mvx, "S-%s-scaled_amax-%s-%d" % (kn, tn, rep), mvx.MVX_SCALED_SUM, t, k, shape, 64 * MIB, 2, reps=10,
+                    warm=2, amax=word)
+
+
 def main():
     mvx = importlib.import_module("mvapich-cce_amd")
+    if "scaled" in sys.argv[1:]:
+        scaled(mvx)
+        return
     if "avg" in sys.argv[1:]:
         avg(mvx)
         return
