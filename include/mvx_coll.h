@@ -248,6 +248,26 @@ int mvx_op_free(MPI_Op *op);
  * Such calls always run directly, never from a captured graph. */
 int mvx_op_create_scaled_sum(const float *rank_scale, int nranks, float out_scale,
                              void *amax_dev /* 4-byte aligned device word, or NULL */, MPI_Op *op);
+/* EXTENSION: a stochastically rounded f32 SUM for tensors that travel as
+ * narrow floats.  The combine is MVX_SUM_ACC32's -- the same program, the
+ * same order, leaves folded as there -- but its f32 value is narrowed to one
+ * of its two neighbours in the type, the upper one with a probability equal
+ * (to nb = 8 or 16 bits) to the value's distance from the lower one in units
+ * of their gap, so the expected stored value is the f32 sum where round to
+ * nearest sends every step's sum to the same side.  The random bits are a
+ * counter-based function of (seed, index of the element in the collective's
+ * reduced vector) alone -- mvx_hip.h, MVX_SR_SUM, has the definition -- so a
+ * call is as reproducible as every other: the same bits on every rank,
+ * exchange variant, buffer kind and slicing.  The index runs over 0..count-1
+ * in Allreduce, Reduce and Scan, and over the concatenation of all ranks'
+ * pieces in Reduce_scatter.  Defined on MVX_FLOAT16, MVX_BFLOAT16,
+ * MVX_FLOAT8_E4M3 and MVX_FLOAT8_E5M2; every other type answers 329.  The
+ * handle comes from the user-op table (MPI_Op_free frees it), holds no state
+ * that a call changes, and is planned as MPI_SUM.  Every rank passes the same
+ * seed (not checked); a caller that wants fresh bits per step makes a handle
+ * per step or folds the step into the seed.  Such calls run directly, never
+ * from a captured graph (a graph would keep a freed handle's seed). */
+int mvx_op_create_sr_sum(unsigned long long seed, MPI_Op *op);
 /* GPUs visible to this process */
 int mvx_device_count(void);
 int MPI_Error_class(int errorcode, int *errorclass);

@@ -81,6 +81,9 @@ int mvx_op_free(int *op);
 /* a per-rank scaled SUM with a fused amax (mvx_coll.h has the semantics);
  * mvx_op_free frees the handle */
 int mvx_op_create_scaled_sum(const float *rank_scale, int nranks, float out_scale, void *amax_dev, int *op);
+/* a stochastically rounded f32 SUM (mvx_coll.h has the semantics); mvx_op_free
+ * frees the handle */
+int mvx_op_create_sr_sum(unsigned long long seed, int *op);
 
 /* The datatype handle a user function receives for libmvx type `type`
  * (default: `type` itself).  A binding that rebuilds the host MPI's derived

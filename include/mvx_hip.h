@@ -228,6 +228,37 @@ int mvx_op_program_scaled(int dtype, const void *const *srcs, const void *const 
                           const float *leaf_scale, const float *fold_scale, float out_scale,
                           void *amax_dev, void *hip_stream);
 
+/* The stochastically rounded f32 sum, a device-layer op index (at the MPI
+ * layer 170 is MPI_ERR_OP: there the op is a handle of mvx_op_create_sr_sum,
+ * mvx_coll.h).  MVX_SUM_ACC32's program and f32 value v, narrowed not to the
+ * nearest value of dtype but to one of its two neighbours lo <= |v| < lo + q,
+ * q = 2^(max(floor(log2 |v|), emin) - m): with f = (|v| - lo) / q,
+ * t = floor(f * 2^nb) and r the element's nb random bits, the magnitude is
+ * lo + q if t + r >= 2^nb, else lo; the sign is v's.  A magnitude past the
+ * largest finite one is the type's overflow (inf; NaN on E4M3); +-0, inf and
+ * NaN narrow as MVX_SUM_ACC32 narrows them; a representable v is never
+ * changed.  Element i of the reduced vector -- dst[j] is element
+ * first_index + j -- draws
+ *   8-bit floats : nb = 8,  r = (H(i >> 2) >> 8 * (i & 3)) & 0xff
+ *   16-bit floats: nb = 16, r = (H(i >> 1) >> 16 * (i & 1)) & 0xffff
+ * with H(g) = fmix32((lo32(g) ^ lo32(seed)) * 0x9E3779B1 + c),
+ * c = fmix32(hi32(g) ^ hi32(seed) ^ 0x85EBCA77) and fmix32 MurmurHash3's
+ * 32-bit finaliser: a function of (seed, i) and of nothing else, so the bits
+ * of the result do not depend on the grid, the kernel, the operands'
+ * alignment or where a vector is cut into launches.  Defined on the four
+ * narrow floating types; every other type is 329.  A lone unfolded leaf is
+ * copied.  Through mvx_op_apply, mvx_op_program, mvx_op_program_f32 and
+ * mvx_op_plan the op runs with seed 0 and first index 0.  The full form:
+ *   side 0          : leaves and dst of dtype.
+ *   side MVX_F32_OUT: MVX_SUM_ACC32's (nothing is narrowed, nothing drawn).
+ *   side MVX_F32_IN : leaves n floats each, never folded; the result rounded
+ *                     as above.
+ * Return codes of mvx_op_program_f32. */
+#define MVX_SR_SUM 170
+int mvx_op_program_sr(int dtype, const void *const *srcs, const void *const *fold, int k,
+                      unsigned tree_mask, unsigned chain_mask, void *dst, size_t n, int side,
+                      unsigned long long seed, unsigned long long first_index, void *hip_stream);
+
 /* What mvx_op_program would launch for these arguments, without launching:
  * the same checks and return codes, then the kernel template as rocprofv3
  * names it, the short tag, the grid and the dynamic LDS reservation.  Only

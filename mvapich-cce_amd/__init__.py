@@ -132,6 +132,8 @@ def _load():
     _hip.mvx_op_program_scaled.argtypes = [i, pvp, pvp, i, ctypes.c_uint, ctypes.c_uint, vp, sz, i,
                                            ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                            ctypes.c_float, vp, vp]
+    _hip.mvx_op_program_sr.argtypes = [i, pvp, pvp, i, ctypes.c_uint, ctypes.c_uint, vp, sz, i,
+                                       ctypes.c_ulonglong, ctypes.c_ulonglong, vp]
     _hip.mvx_tree_mask.argtypes = [i]
     _hip.mvx_tree_mask.restype = ctypes.c_uint
     _hip.mvx_chain_mask.argtypes = [i]
@@ -194,6 +196,7 @@ def _load():
     c.MPI_Op_create.argtypes = [vp, i, pi]
     c.mvx_op_create_device.argtypes = [vp, i, pi]
     c.mvx_op_create_scaled_sum.argtypes = [ctypes.POINTER(ctypes.c_float), i, ctypes.c_float, vp, pi]
+    c.mvx_op_create_sr_sum.argtypes = [ctypes.c_ulonglong, pi]
     c.MPI_Op_free.argtypes = [pi]
     c.MPI_Error_class.argtypes = [i, pi]
     c.mvx_allreduce_async.argtypes = [vp, vp, i, i, i, i, vp]

@@ -10,8 +10,8 @@ from . import coll, hip
 from .consts import COLL_ALLREDUCE, COLL_REDUCE, COLL_REDUCE_SCATTER  # noqa: F401
 
 __all__ = [
-    "addr", "stream_handle", "op_apply", "op_combine", "op_program", "op_program_f32", "op_program_avg", "op_program_scaled", "op_plan", "LaunchPlan", "Comm",
-    "MPI_Allreduce", "MPI_Reduce", "MPI_Reduce_scatter", "MPI_Scan", "MPI_Op_create", "MPI_Op_free", "op_create_device", "op_create_scaled_sum",
+    "addr", "stream_handle", "op_apply", "op_combine", "op_program", "op_program_f32", "op_program_avg", "op_program_scaled", "op_program_sr", "op_plan", "LaunchPlan", "Comm",
+    "MPI_Allreduce", "MPI_Reduce", "MPI_Reduce_scatter", "MPI_Scan", "MPI_Op_create", "MPI_Op_free", "op_create_device", "op_create_scaled_sum", "op_create_sr_sum",
     "MPIR_call", "op_errno", "last_kernel", "last_kernel_symbol", "last_launch", "set_launch",
     "set_fortran_logical", "comm_reap", "host_register_enable", "host_unregister", "host_register_stats",
     "host_hooks_active", "host_invalidate", "host_register_deferred",
@@ -101,6 +101,15 @@ def op_program_scaled(dtype, srcs, dst, n, tree_mask, chain_mask, leaf_scale, ou
     return hip().mvx_op_program_scaled(dtype, _pp(srcs), fo, len(srcs), tree_mask, chain_mask, addr(dst), n, side,
                                        ls, fs, out_scale, addr(amax) if amax is not None else None,
                                        stream_handle(stream))
+
+
+def op_program_sr(dtype, srcs, dst, n, tree_mask, chain_mask, seed, first_index=0, side=0, folds=None, stream=None):
+    """MVX_SR_SUM's combine program (mvx_op_program_sr): MVX_SUM_ACC32's f32
+    value, stochastically rounded with the bits of (seed, first_index + j) for
+    dst[j].  side 0, F32_OUT (nothing rounded) or F32_IN as in op_program_f32."""
+    fo = _pp(folds) if folds is not None else None
+    return hip().mvx_op_program_sr(dtype, _pp(srcs), fo, len(srcs), tree_mask, chain_mask, addr(dst), n, side,
+                                   seed, first_index, stream_handle(stream))
 
 
 class LaunchPlan(ctypes.Structure):
@@ -426,6 +435,15 @@ def op_create_scaled_sum(rank_scale, out_scale=1.0, amax=None, nranks=None):
     rs = (ctypes.c_float * max(len(rank_scale), 1))(*rank_scale)
     rc = coll().mvx_op_create_scaled_sum(rs, len(rank_scale) if nranks is None else nranks, out_scale,
                                          addr(amax) if amax is not None else None, ctypes.byref(h))
+    return rc, h.value
+
+
+def op_create_sr_sum(seed):
+    """mvx_op_create_sr_sum: a stochastically rounded f32 SUM whose random bits
+    are a function of (seed, element index).  Returns (rc, op_handle);
+    MPI_Op_free frees the handle."""
+    h = ctypes.c_int(0)
+    rc = coll().mvx_op_create_sr_sum(seed, ctypes.byref(h))
     return rc, h.value
 
 

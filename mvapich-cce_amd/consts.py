@@ -32,6 +32,9 @@ MVX_AVG = 168
 # device-layer op index (include/mvx_hip.h) of the per-rank scaled sum; at the MPI layer the op is a
 # handle of op_create_scaled_sum and 169 is MPI_ERR_OP
 MVX_SCALED_SUM = 169
+# device-layer op index of the stochastically rounded f32 sum; at the MPI layer the op is a handle of
+# op_create_sr_sum and 170 is MPI_ERR_OP
+MVX_SR_SUM = 170
 F32_OUT, F32_IN = 1, 2                       # mvx_op_program_f32's side (include/mvx_hip.h)
 
 MPI_COMM_WORLD, MPI_COMM_SELF = 91, 92
@@ -126,6 +129,8 @@ DEFINED_ACC32 = {op: _HALFS + _FP8S for op in (MVX_SUM_ACC32, MVX_PROD_ACC32)}
 DEFINED_AVG = {MVX_AVG: [MPI_FLOAT, MPI_DOUBLE, MPI_REAL, MPI_DOUBLE_PRECISION] + _HALFS + _FP8S}
 # the scaled sum: the f32 kind and the four narrow floats (there is no f64 form: scales are floats)
 DEFINED_SCALED = {MVX_SCALED_SUM: [MPI_FLOAT, MPI_REAL] + _HALFS + _FP8S}
+# the stochastically rounded sum: the four narrow floats alone
+DEFINED_SR = {MVX_SR_SUM: _HALFS + _FP8S}
 DEVICE_TYPES = sorted(NP_DTYPE)
 
 # mvx_comm_set_call_kinds (include/mvx_embed.h)

@@ -5,7 +5,8 @@
  * same association (the f32-accumulating extension ops through f32
  * temporaries, so nothing is narrowed before the end; MVX_AVG as its sum,
  * divided in the last launch; a scaled sum with its ranks' scales on the raw
- * leaves and its output scale and amax in the last launch); user functions get
+ * leaves and its output scale and amax in the last launch; a stochastically
+ * rounded sum as MVX_SUM_ACC32, rounded with its seed in the last launch); user functions get
  * the reference's operand roles (host MPI_User_functions through pinned
  * scratch, device functions in HBM); datatypes with holes are unpacked to the extent layout the op sees.
  * Reference: the (*uop) calls of intra_fns_new.c (e.g. 5505-5512, 5681-5699)
@@ -152,7 +153,12 @@ static char *scratch_take(scratch_t *S)
  * same slots, on MPI_FLOAT too: every launch that reads raw leaves -- the
  * 1-leaf widening one included -- multiplies them by their ranks' scales
  * (MVX_F32_OUT), f32 to f32 rounds are MPI_SUM on MPI_FLOAT, and the last
- * launch applies the output scale and takes amax. */
+ * launch applies the output scale and takes amax.
+ *
+ * A stochastically rounded sum (mvx_op_create_sr_sum) is MVX_SUM_ACC32 until
+ * the program's last launch, which narrows with the handle's seed and, as the
+ * index of its first element in the reduced vector, the block's offset
+ * c_src_off (a slice's under `pipe`: mvxi_plan_slice moves it along). */
 #define DST_WIDE 1   /* dst takes the f32 value (a temporary of an f32-accumulating program) */
 #define DST_LAST 2   /* dst is the program's result */
 
@@ -169,9 +175,9 @@ static int launch_prog(const mvx_plan *P, leafref *v, int m, unsigned tmask,
     const void *srcs[MVX_COMBINE_KMAX], *fold[MVX_COMBINE_KMAX];
     const size_t n = (size_t)P->c_cnt;
     const int dst_wide = dflags & DST_WIDE, avg = mvxi_avg(P->op);
-    const mvx_op_t *sc = mvxi_scaled(P->op);
-    /* every launch but AVG's last; a scaled sum's f32 to f32 rounds */
-    const int op = sc ? MVX_SUM_ACC32 : !avg ? P->op : mvxi_wide_f32(P) ? MVX_SUM_ACC32 : MPI_SUM;
+    const mvx_op_t *sc = mvxi_scaled(P->op), *sr = mvxi_sr(P->op);
+    /* every launch but AVG's and SR's last; a scaled sum's f32 to f32 rounds */
+    const int op = sc || sr ? MVX_SUM_ACC32 : !avg ? P->op : mvxi_wide_f32(P) ? MVX_SUM_ACC32 : MPI_SUM;
     float ls[MVX_COMBINE_KMAX], fs[MVX_COMBINE_KMAX];
     int q, nw = 0, rc;
     if (!dst) return MPI_ERR_INTERN;
@@ -199,6 +205,9 @@ static int launch_prog(const mvx_plan *P, leafref *v, int m, unsigned tmask,
         return mvx_op_program_scaled(P->dtype, srcs, nw ? NULL : fold, m, tmask, cmask, dst, n,
                                      dst_wide ? MVX_F32_OUT : nw ? MVX_F32_IN : 0, ls, fs,
                                      (dflags & DST_LAST) ? sc->out_scale : 1.0f, (dflags & DST_LAST) ? sc->amax : NULL, st);
+    if (sr && (dflags & DST_LAST))
+        return mvx_op_program_sr(P->dtype, srcs, nw ? NULL : fold, m, tmask, cmask, dst, n, nw ? MVX_F32_IN : 0,
+                                 sr->seed, (unsigned long long)P->c_src_off, st);
     if (avg && (dflags & DST_LAST))
         return mvx_op_program_avg(P->dtype, srcs, nw ? NULL : fold, m, tmask, cmask, dst, n, nw ? MVX_F32_IN : 0,
                                   avg_divisor(P), st);
@@ -370,7 +379,7 @@ int mvxi_combine(mvx_comm_t *c, const mvx_plan *P, const char *const *leafp, voi
                    scratch_t *S, hipStream_t st)
 {
     const void *srcs[MVX_MAXK], *fold[MVX_MAXK];
-    const mvx_op_t *sc;
+    const mvx_op_t *sc, *sr;
     unsigned tm, cm;
     int q;
     for (q = 0; q < P->k; q++) {
@@ -401,5 +410,8 @@ int mvxi_combine(mvx_comm_t *c, const mvx_plan *P, const char *const *leafp, voi
         return mvx_op_program_scaled(P->dtype, srcs, fold, P->k, tm, cm, dst, (size_t)P->c_cnt, 0, ls, fs,
                                      sc->out_scale, sc->amax, st);
     }
+    if ((sr = mvxi_sr(P->op)))
+        return mvx_op_program_sr(P->dtype, srcs, fold, P->k, tm, cm, dst, (size_t)P->c_cnt, 0, sr->seed,
+                                 (unsigned long long)P->c_src_off, st);
     return mvx_op_program(P->op, P->dtype, srcs, fold, P->k, tm, cm, dst, (size_t)P->c_cnt, st);
 }

@@ -225,7 +225,8 @@ static int graph_forked(hipGraph_t g)
 static int graph_eligible(const mvx_comm_t *c, const job_t *J)
 {
     return c->graphs && !c->graph_error && J->nr == 1 && !c->local && !c->has_ops && c->nccl && !c->timing &&
-           J->P[0].opkind == MVX_OPKIND_PREDEFINED && !mvxi_scaled(J->P[0].op) && !J->P[0].packed &&
+           J->P[0].opkind == MVX_OPKIND_PREDEFINED && !mvxi_scaled(J->P[0].op) && !mvxi_sr(J->P[0].op) &&
+           !J->P[0].packed &&
            (c->exch != MVX_EXCH_PIPE || c->graph_fork);
 }
 

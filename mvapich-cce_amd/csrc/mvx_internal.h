@@ -334,6 +334,10 @@ typedef struct {           /* struct MPIR_OP, include/mpiops.h:1-11 */
     float out_scale;
     void *amax;                /* the caller's device word, or NULL */
     float rank_scale[MVX_MAXP];
+    /* a stochastically rounded sum (mvx_op_create_sr_sum): no function either,
+     * planned the same way, combined by MVX_SR_SUM's kernels with this seed */
+    int sr;
+    unsigned long long seed;
 } mvx_op_t;
 
 MVXI int mvxi_predefined(MPI_Op op);
@@ -344,6 +348,8 @@ static inline int mvxi_avg(MPI_Op op) { return op == MVX_AVG; }
 MVXI mvx_op_t *mvxi_user_op(MPI_Op op);
 /* the op's entry if it is a scaled sum, else NULL */
 MVXI const mvx_op_t *mvxi_scaled(MPI_Op op);
+/* the op's entry if it is a stochastically rounded sum, else NULL */
+MVXI const mvx_op_t *mvxi_sr(MPI_Op op);
 MVXI int mvxi_op_kind(MPI_Op op);
 MVXI int mvxi_op_verdict(MPI_Op op, MPI_Datatype dt);
 MVXI MPI_Datatype mvxi_user_handle(MPI_Datatype dt);
@@ -360,10 +366,12 @@ MVXI int mvxi_wide_temps(const mvx_plan *P);
  * 16-byte boundary of the floats (mvx_ops.hip: split, split_f32) */
 /* the plan's intermediates are f32 temporaries: the f32-accumulating ops,
  * MVX_AVG on the narrow floats (its other types are 4 and 8 bytes), and a
- * scaled sum on every type it has (MPI_FLOAT's own format) */
+ * scaled sum on every type it has (MPI_FLOAT's own format), and a
+ * stochastically rounded sum (rounded once, at the end) */
 static inline int mvxi_wide_f32(const mvx_plan *P)
 {
-    return mvxi_acc32(P->op) || (mvxi_avg(P->op) && P->esize < 4) || mvxi_scaled(P->op) != NULL;
+    return mvxi_acc32(P->op) || (mvxi_avg(P->op) && P->esize < 4) || mvxi_scaled(P->op) != NULL ||
+           mvxi_sr(P->op) != NULL;
 }
 static inline size_t mvxi_wide_esize(const mvx_plan *P) { return mvxi_wide_f32(P) ? 4 : (size_t)P->esize; }
 static inline size_t mvxi_wide_residue(const mvx_plan *P, const void *like)

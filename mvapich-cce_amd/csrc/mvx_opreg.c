@@ -28,6 +28,12 @@ const mvx_op_t *mvxi_scaled(MPI_Op op)
     return o && o->scaled ? o : NULL;
 }
 
+const mvx_op_t *mvxi_sr(MPI_Op op)
+{
+    const mvx_op_t *o = mvxi_user_op(op);
+    return o && o->sr ? o : NULL;
+}
+
 static int op_register(MPI_User_function *fn, MVX_Device_function *dfn, int commute, MPI_Op *op)
 {
     int i;
@@ -40,6 +46,7 @@ static int op_register(MPI_User_function *fn, MVX_Device_function *dfn, int comm
             g_user_ops[i].commute = commute;
             g_user_ops[i].permanent = 0;
             g_user_ops[i].scaled = 0;
+            g_user_ops[i].sr = 0;
             *op = USER_OP_BASE + i;
             return MPI_SUCCESS;
         }
@@ -80,6 +87,18 @@ int mvx_op_create_scaled_sum(const float *rank_scale, int nranks, float out_scal
     return MPI_SUCCESS;
 }
 
+/* EXTENSION (mvx_coll.h): a handle of the user-op table that carries the seed */
+int mvx_op_create_sr_sum(unsigned long long seed, MPI_Op *op)
+{
+    mvx_op_t *o;
+    int rc;
+    if ((rc = op_register(NULL, NULL, 1, op))) return rc;
+    o = mvxi_user_op(*op);
+    o->sr = 1;
+    o->seed = seed;
+    return MPI_SUCCESS;
+}
+
 int MPI_Op_free(MPI_Op *op)  /* opfree.c:51-82 */
 {
     mvx_op_t *o;
@@ -100,7 +119,7 @@ int mvx_op_free(MPI_Op *op) { return MPI_Op_free(op); }
 int mvxi_op_kind(MPI_Op op)
 {
     const mvx_op_t *o = mvxi_predefined(op) ? NULL : mvxi_user_op(op);
-    if (!o || o->scaled) return MVX_OPKIND_PREDEFINED;
+    if (!o || o->scaled || o->sr) return MVX_OPKIND_PREDEFINED;
     return o->commute ? MVX_OPKIND_USER_COMMUTE : MVX_OPKIND_USER_NONCOMMUTE;
 }
 
@@ -111,6 +130,7 @@ int mvxi_op_verdict(MPI_Op op, MPI_Datatype dt)
 {
     if (mvxi_predefined(op)) return mvx_op_apply(op, dt, NULL, NULL, 0, NULL);
     if (mvxi_scaled(op)) return mvx_op_apply(MVX_SCALED_SUM, dt, NULL, NULL, 0, NULL);
+    if (mvxi_sr(op)) return mvx_op_apply(MVX_SR_SUM, dt, NULL, NULL, 0, NULL);
     return mvxi_user_op(op) ? MPI_SUCCESS : MPI_ERR_OP;
 }
 

@@ -5,7 +5,7 @@
 // never touch the device or a buffer; run() is the one place that launches.
 // mvx_op_plan answers with the plan alone.  The kernels are in mvx_ops_kern.h
 // (design notes at its top), their host-side tables in mvx_ops_tab.h and
-// mvx_ops_{cmp,arith,logic,loc,half,fp8,acc32,avg,scaled}.hip.
+// mvx_ops_{cmp,arith,logic,loc,half,fp8,acc32,avg,scaled,sr}.hip.
 #include <stdlib.h>
 
 #include "mvx_dtype.h"
@@ -108,7 +108,8 @@ static int ekind(int dtype)
 // handle outside MPI_MAX..MPI_MAXLOC that is not one of the extension
 // ops.  MVX_SUM_ACC32 and MVX_PROD_ACC32 have a case for the four
 // narrow floating types alone; MVX_AVG has those and the f32 / f64 kinds;
-// the device-layer index MVX_SCALED_SUM those four and the f32 kind.
+// the device-layer index MVX_SCALED_SUM those four and the f32 kind, and
+// MVX_SR_SUM the four alone.
 static bool acc32(int op) { return op == MVX_SUM_ACC32 || op == MVX_PROD_ACC32; }
 
 static const KSet *lookup(int op, int dtype, int *rc)
@@ -118,6 +119,7 @@ static const KSet *lookup(int op, int dtype, int *rc)
     if (acc32(op)) return lookup_acc32(op, ek);
     if (op == MVX_AVG) return lookup_avg(ek);
     if (op == MVX_SCALED_SUM) return lookup_scaled(ek);
+    if (op == MVX_SR_SUM) return lookup_sr(ek);
     if (ek == EK_LOGICAL && (op == MPI_BAND || op == MPI_BOR || op == MPI_BXOR))
         ek = EK_U32;                 // bitwise on the MPI_Fint word
     if (ek == EK_F16 || ek == EK_BF16) {
@@ -261,6 +263,7 @@ struct Plan {
     unsigned blocks;
     size_t lds;            // dynamic LDS bytes: the residency cap
     bool body;             // the kernel takes BodyParams
+    bool sr;               // MVX_SR_SUM's: RParams / RBodyParams
 };
 
 // P with split()'s answer in it; nfold of its leaves are folded.
@@ -284,6 +287,7 @@ static Plan plan(const KSet *ks, const KFam &F, const Params &P, int nfold, cons
     pl.blocks = (unsigned)(work < cfg.block_cap ? work : cfg.block_cap);
     pl.lds = body ? cap_lds(V.cap) : nt ? cap_lds((int)fam_cap[F.fam]) : 0;
     pl.body = body;
+    pl.sr = ks->sr;
     return pl;
 }
 
@@ -304,12 +308,30 @@ static Plan plan_params(const KSet *ks, Params &P)
 static Plan g_last;        // the last launch (not thread-safe)
 
 // (P and B are the scaled sum's parameter structs, which begin with every
-// other kernel's: a kernel takes as many bytes as its own argument has)
-static int run(const Plan &pl, const SParams &P, hipStream_t stream)
+// other kernel's: a kernel takes as many bytes as its own argument has.
+// MVX_SR_SUM's kernels have other fields behind the common ones: `sr`, or seed
+// 0 and first index 0 through the entry points that take none.)
+static int run(const Plan &pl, const SParams &P, hipStream_t stream, const Sr *sr = nullptr)
 {
     SBodyParams B;
+    RParams R;
+    RBodyParams RB;
     void *args[] = {const_cast<SParams *>(&P)};
-    if (pl.body) {
+    if (pl.sr) {
+        static_cast<Params &>(R) = P;
+        R.sr = sr ? *sr : Sr{0u, 0u, 0u};
+        args[0] = &R;
+    }
+    if (pl.body && pl.sr) {
+        memset(&RB, 0, sizeof RB);
+        for (int q = 0; q < P.k; ++q) RB.src[q] = reinterpret_cast<const u32x4 *>(P.src[q]);
+        RB.dst = reinterpret_cast<u32x4 *>(P.dst);
+        RB.nvec = P.nvec;
+        RB.k = P.k;
+        RB.divisor = P.divisor;
+        RB.sr = R.sr;
+        args[0] = &RB;
+    } else if (pl.body) {
         memset(&B, 0, sizeof B);
         for (int q = 0; q < P.k; ++q) B.src[q] = reinterpret_cast<const u32x4 *>(P.src[q]);
         B.dst = reinterpret_cast<u32x4 *>(P.dst);
@@ -408,6 +430,7 @@ static Plan plan_f32(const KSet *ks, Params &P, bool f32_out, const Config &cfg)
     pl.blocks = (unsigned)(work < cfg.block_cap ? work : cfg.block_cap);
     pl.lds = 0;
     pl.body = false;
+    pl.sr = ks->sr;
     return pl;
 }
 
@@ -491,13 +514,18 @@ extern "C" int mvx_op_program_f32(int op, int dtype, const void *const *srcs, co
 {
     const KSet *ks;
     SParams P;
+    int rc0;
     const int rc = program_params(op, dtype, srcs, fold, k, tree_mask, chain_mask, dst, n, &ks, P);
     if (rc != MPI_SUCCESS) return rc;
-    /* only the f32-accumulating ops (and the scaled sum, here with unit scales) have an f32 side */
-    if ((!acc32(op) && op != MVX_SCALED_SUM) || (side != MVX_F32_OUT && side != MVX_F32_IN)) return MPI_ERR_ARG;
+    /* only the f32-accumulating ops (and the scaled sum, here with unit scales, and the
+     * stochastically rounded one, here with seed 0 and first index 0) have an f32 side */
+    if ((!acc32(op) && op != MVX_SCALED_SUM && op != MVX_SR_SUM) || (side != MVX_F32_OUT && side != MVX_F32_IN))
+        return MPI_ERR_ARG;
     if (!ks) return MPI_SUCCESS;
     if (f32side_args(P, side)) return MPI_ERR_ARG;
     if (op == MVX_SCALED_SUM) return run_scaled(ks, P, side, (hipStream_t)stream);
+    /* nothing is narrowed, so nothing is drawn: MVX_SUM_ACC32's kernel */
+    if (op == MVX_SR_SUM && side == MVX_F32_OUT) ks = lookup(MVX_SUM_ACC32, dtype, &rc0);
     return run(plan_f32(ks, P, side == MVX_F32_OUT, config()), P, (hipStream_t)stream);
 }
 
@@ -524,6 +552,23 @@ extern "C" int mvx_op_program_scaled(int dtype, const void *const *srcs, const v
     P.sc.oscale = out_scale;
     P.sc.amax = (unsigned *)amax_dev;
     return run_scaled(ks, P, side, (hipStream_t)stream);
+}
+
+extern "C" int mvx_op_program_sr(int dtype, const void *const *srcs, const void *const *fold, int k,
+                                 unsigned tree_mask, unsigned chain_mask, void *dst, size_t n, int side,
+                                 unsigned long long seed, unsigned long long first_index, void *stream)
+{
+    if (side == MVX_F32_OUT)
+        return mvx_op_program_f32(MVX_SR_SUM, dtype, srcs, fold, k, tree_mask, chain_mask, dst, n, side, stream);
+    const KSet *ks;
+    SParams P;
+    const int rc = program_params(MVX_SR_SUM, dtype, srcs, fold, k, tree_mask, chain_mask, dst, n, &ks, P);
+    if (rc != MPI_SUCCESS) return rc;
+    if (side != 0 && side != MVX_F32_IN) return MPI_ERR_ARG;
+    if (!ks) return MPI_SUCCESS;
+    if (f32side_args(P, side)) return MPI_ERR_ARG;
+    const Sr sr = {(uint32_t)seed, (uint32_t)(seed >> 32), (uint64_t)first_index};
+    return run(side ? plan_f32(ks, P, false, config()) : plan_params(ks, P), P, (hipStream_t)stream, &sr);
 }
 
 extern "C" int mvx_op_program_avg(int dtype, const void *const *srcs, const void *const *fold, int k,

@@ -4,8 +4,9 @@
 // Chunk / CG, the chunk op CF with its SWAR, packed-16 and 8-bit float forms.
 // Last, the wide accumulator of the f32-accumulating ops (Wide, acc_steps,
 // acc_chunk), MVX_AVG's finalising division (avg_fin, avg_chunk) and the
-// scaled sum's scales and amax (Scl, scl_amax, wave_umax).  Device
-// code only; the kernels that use them are in
+// scaled sum's scales and amax (Scl, scl_amax, wave_umax) and the stochastically
+// rounded sum's counter-based bits and integer narrowing (Sr, sr_word_bits,
+// sr_code).  Device code only; the kernels that use them are in
 // mvx_ops_kern.h (design notes there).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -26,8 +27,12 @@ enum { OMAX = 0, OMIN, OSUM, OPROD, OLAND, OBAND, OLOR, OBOR, OLXOR, OBXOR,
        // extension (MVX_SCALED_SUM): the f32 SUM program over leaves multiplied
        // by their ranks' scales, its value rescaled once, with a fused amax
        // (the end of this file)
-       OSCL };
-static_assert(OAVG == 14 && OSCL == 15, "");
+       OSCL,
+       // extension (MVX_SR_SUM): MVX_SUM_ACC32's f32 value narrowed by stochastic
+       // rounding, the random bits a function of (seed, element index) alone
+       // (the end of this file)
+       OSR };
+static_assert(OAVG == 14 && OSCL == 15 && OSR == 16, "");
 
 // Element layouts: the reference's C types on x86-64 LP64.
 struct cf32 { float re, im; };                          // global_ops.c:43-46
@@ -580,7 +585,7 @@ template <typename T> struct narrow_float {
 };
 // the (op, type) pairs whose program runs on widened f32 values
 template <int O, typename T> struct acc_op {
-    static constexpr bool v = O == OSUMA || O == OPRODA || (O == OAVG && narrow_float<T>::v) || O == OSCL;
+    static constexpr bool v = O == OSUMA || O == OPRODA || (O == OAVG && narrow_float<T>::v) || O == OSCL || O == OSR;
 };
 
 // MVX_SCALED_SUM (OSCL), the per-rank scaled sum: the f32 program above with
@@ -662,7 +667,7 @@ __device__ __forceinline__ bool scl_unit(const Scl &sc) { return sc.lscale[0] ==
 template <int O>
 __device__ __forceinline__ float accf(float a, float b)
 {
-    static_assert(O == OSUMA || O == OPRODA || O == OAVG || O == OSCL, "");
+    static_assert(O == OSUMA || O == OPRODA || O == OAVG || O == OSCL || O == OSR, "");
     return O == OPRODA ? a * b : a + b;
 }
 
@@ -889,6 +894,181 @@ __device__ __forceinline__ unsigned amax_chunk(const Chunk<T> &x)
         am = scl_amax(am, y);
     }
     return am;
+}
+
+// MVX_SR_SUM (OSR), the stochastically rounded sum: MVX_SUM_ACC32's program
+// and f32 value, narrowed to one of its two neighbours in T with probability
+// proportional to the distance to the other (DESIGN.md section 7 has the
+// definition the bits are held to).  The random bits are no generator's state
+// but a counter-based function of (seed, index of the element in the
+// collective's reduced vector): whatever the grid, the kernel family, the
+// operands' alignment or the cut of a launch, an element draws the same bits.
+// One 32-bit hash H(g) serves the group g of L elements that share a word
+// (L = 4 or 2), so the chunk path pays one hash a word -- or, where the words
+// of a launch start `o` elements into a group, the hashes of both groups a
+// word straddles, funnel-shifted (v_alignbit) into the word's bits; adjacent
+// words share a hash, 5 for a chunk.  H's inner constant c depends on the high
+// half of g alone and stays in a register from chunk to chunk (SrC).
+struct Sr {
+    uint32_t s0, s1;      // the seed's halves
+    uint64_t first;       // index of dst[0] in the reduced vector
+};
+template <int O, typename PT>
+__device__ __forceinline__ const Sr &sr_of(const PT &P) { return P.sr; }
+
+__device__ __forceinline__ uint32_t fmix32(uint32_t h)
+{
+    h ^= h >> 16;
+    h *= 0x85EBCA6Bu;
+    h ^= h >> 13;
+    h *= 0xC2B2AE35u;
+    h ^= h >> 16;
+    return h;
+}
+__device__ __forceinline__ uint32_t sr_c(const Sr &sr, uint32_t hi) { return fmix32(hi ^ sr.s1 ^ 0x85EBCA77u); }
+__device__ __forceinline__ uint32_t sr_h(const Sr &sr, uint32_t lo, uint32_t c)
+{
+    return fmix32((lo ^ sr.s0) * 0x9E3779B1u + c);
+}
+__device__ __forceinline__ uint32_t sr_hash(const Sr &sr, uint64_t g)
+{
+    return sr_h(sr, (uint32_t)g, sr_c(sr, (uint32_t)(g >> 32)));
+}
+
+// the target formats: mantissa bits, exponent bias, random bits an element
+// draws, the code every magnitude past the largest finite one gets (inf; NaN
+// on E4M3, which has no inf), bits of an element
+template <typename T> struct SrFmt;
+template <> struct SrFmt<f16> { static constexpr int M = 10, BIAS = 15, NB = 16, OVF = 0x7c00, BITS = 16; };
+template <> struct SrFmt<bf16> { static constexpr int M = 7, BIAS = 127, NB = 16, OVF = 0x7f80, BITS = 16; };
+template <> struct SrFmt<f8e4m3> { static constexpr int M = 3, BIAS = 7, NB = 8, OVF = 0x7f, BITS = 8; };
+template <> struct SrFmt<f8e5m2> { static constexpr int M = 2, BIAS = 15, NB = 8, OVF = 0x7c, BITS = 8; };
+
+// the lane's c, kept while the high half of the group index stays
+struct SrC { uint32_t hi, c; };
+__device__ __forceinline__ SrC src_none() { return {0xffffffffu, 0u}; }   // (no group index is that high)
+
+// the bits of element i alone (heads, tails, the element path)
+template <typename T>
+__device__ __forceinline__ uint32_t sr_elt_bits(const Sr &sr, uint64_t i)
+{
+    constexpr int L = Wide<T>::L, NB = SrFmt<T>::NB;
+    return (sr_hash(sr, i / L) >> (NB * (int)(i & (L - 1)))) & ((1u << NB) - 1);
+}
+
+// the bits of N consecutive words of elements, the first of which is element
+// i0 of the reduced vector, o = i0 % L elements into its group (uniform over
+// the launch: a scalar branch)
+template <typename T, int N>
+__device__ __forceinline__ void sr_word_bits(const Sr &sr, uint64_t i0, int o, SrC &cc, uint32_t (&rb)[N])
+{
+    constexpr int L = Wide<T>::L, NB = SrFmt<T>::NB;
+    const uint64_t g0 = i0 / L;
+    const uint32_t lo0 = (uint32_t)g0, hi0 = (uint32_t)(g0 >> 32);
+    uint32_t h[N + 1];
+    if (lo0 > 0xffffffffu - N) {          // the high half changes inside: c per hash
+#pragma unroll
+        for (int j = 0; j <= N; ++j) h[j] = sr_hash(sr, g0 + j);
+    } else {
+        if (hi0 != cc.hi) {
+            cc.hi = hi0;
+            cc.c = sr_c(sr, hi0);
+        }
+#pragma unroll
+        for (int j = 0; j < N; ++j) h[j] = sr_h(sr, lo0 + j, cc.c);
+        h[N] = o ? sr_h(sr, lo0 + N, cc.c) : 0u;
+    }
+    if (o) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) rb[j] = __builtin_amdgcn_alignbit(h[j + 1], h[j], (uint32_t)(o * NB));
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; ++j) rb[j] = h[j];
+    }
+}
+
+// A finite f32 value's bits u narrowed with r, NB random bits: integer
+// arithmetic on the bit pattern.  With the significand M (implicit one set)
+// shifted so that the target's last kept bit q lands on bit NB, the bits below
+// are floor(f * 2^NB) and adding r carries into q exactly when t + r >= 2^NB;
+// the carry runs on into the exponent, up to the overflow code.  Below the
+// least normal exponent q stays 2^(emin - m): the shift grows by the distance
+// (31 and more shift everything out: the value is below every chance), and
+// the units are the subnormal's code.  bf16 has f32's exponents: its code is
+// the upper half of u + r, subnormals and the carry into inf included.
+template <typename T>
+__device__ __forceinline__ uint32_t sr_code(uint32_t u, uint32_t r)
+{
+    typedef SrFmt<T> Fm;
+    if constexpr (std::is_same<T, bf16>::value) {
+        return (u + r) >> 16;
+    } else {
+        constexpr int SH = 23 - Fm::M, PRE = Fm::NB > SH ? Fm::NB - SH : 0, POST = SH > Fm::NB ? SH - Fm::NB : 0;
+        const int et = (int)((u >> 23) & 0xffu) - (127 - Fm::BIAS);   // the target's biased exponent
+        const uint32_t m = ((u & 0x7fffffu) | 0x800000u) << PRE;
+        const int below = et < 1 ? 1 - et : 0;
+        const int sh = below + POST < 31 ? below + POST : 31;
+        const uint32_t units = ((m >> sh) + r) >> Fm::NB;
+        uint32_t code = ((uint32_t)(et < 1 ? 0 : et - 1) << Fm::M) + units;
+        code = code < (uint32_t)Fm::OVF ? code : (uint32_t)Fm::OVF;
+        return code | ((u >> 31) << (Fm::BITS - 1));
+    }
+}
+
+// a word's L f32 values narrowed with the word's bits rb (element j's in bits
+// NB * j up); inf and NaN go the round-to-nearest way, as they always have
+template <typename T>
+__device__ __forceinline__ uint32_t sr_narrow(const float (&y)[Wide<T>::L], uint32_t rb)
+{
+    constexpr int L = Wide<T>::L, NB = SrFmt<T>::NB, BITS = SrFmt<T>::BITS;
+    constexpr uint32_t RM = (1u << NB) - 1, EM = (1u << BITS) - 1;
+    const uint32_t rne = Wide<T>::narrow(y);
+    uint32_t w = 0;
+#pragma unroll
+    for (int j = 0; j < L; ++j) {
+        const uint32_t u = f32_bits(y[j]);
+        const uint32_t code = sr_code<T>(u, (rb >> (NB * j)) & RM) & EM;
+        const bool finite = (u & 0x7f800000u) != 0x7f800000u;
+        w |= (finite ? code : (rne >> (BITS * j)) & EM) << (BITS * j);
+    }
+    return w;
+}
+
+// the element path's narrow_elt: r is the element's own bits
+template <typename T>
+__device__ __forceinline__ void narrow_elt_sr(T *p, float v, uint32_t r)
+{
+    float y[Wide<T>::L] = {};
+    y[0] = v;
+    const uint32_t w = sr_narrow<T>(y, r);
+    __builtin_memcpy(p, &w, sizeof(T));
+}
+
+// OSR's acc_chunk: the f32 program of acc_chunk<OSUMA>, each word narrowed
+// with its bits rb[w]
+template <typename T, int KMAX, int PROG>
+__device__ __forceinline__ void sr_chunk(Chunk<T> (&x)[KMAX], const Chunk<T> (&xf)[KMAX], unsigned fold_mask,
+                                         int k, unsigned tree_mask, unsigned chain_mask, const uint32_t (&rb)[4])
+{
+    constexpr int L = Wide<T>::L;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        float y[KMAX][L];
+#pragma unroll
+        for (int q = 0; q < KMAX; ++q) {
+            if (PROG == 1 || q < k) {
+                Wide<T>::widen(x[q].w[w], y[q]);
+                if (PROG == 0 && (fold_mask & (1u << q))) {
+                    float f[L];
+                    Wide<T>::widen(xf[q].w[w], f);
+#pragma unroll
+                    for (int j = 0; j < L; ++j) y[q][j] = accf<OSR>(y[q][j], f[j]);
+                }
+            }
+        }
+        acc_steps<OSR, KMAX, L, PROG>(y, k, tree_mask, chain_mask);
+        x[0].w[w] = sr_narrow<T>(y[0], rb[w]);
+    }
 }
 
 // OAVG on float and double: the finalising step on every element of the

@@ -3,7 +3,7 @@
 // path and what they take (Params, BodyParams), written for gfx950 (CDNA4,
 // wave64).  The ops on elements and chunks are in mvx_ops_fn.h; the host-side
 // tables that name every instantiation are in mvx_ops_tab.h, which mvx_ops.hip
-// and the per-op table units mvx_ops_{cmp,arith,logic,loc,half,fp8,acc32,avg,scaled}.hip include.
+// and the per-op table units mvx_ops_{cmp,arith,logic,loc,half,fp8,acc32,avg,scaled,sr}.hip include.
 // Built into libmvx_hip.so; C-ABI in include/mvx_hip.h.
 //
 // One kernel template covers every predefined op x type of the reference
@@ -53,6 +53,10 @@ struct Params {
 // the scaled sum's kernels: the same, with its scales and amax word behind
 struct SParams : Params {
     Scl sc;
+};
+// the stochastically rounded sum's: its seed and the index of dst[0] behind
+struct RParams : Params {
+    Sr sr;
 };
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));  // one dwordx4
@@ -201,6 +205,38 @@ __device__ __forceinline__ void batch_scl(Chunk<T> (&x)[U][KMAX], const u32x4 *(
     }
 }
 
+// OSR's batch_acc, through sr_chunk: chunk c of the body begins at element i0 +
+// c * V of the reduced vector, o elements into a group of L (sr_word_bits).
+template <typename T, int KMAX, int U, int NT, int PROG>
+__device__ __forceinline__ void batch_sr(Chunk<T> (&x)[U][KMAX], const u32x4 *(&fold)[KMAX], long c0,
+                                         long nvec, int k, unsigned tree_mask, unsigned chain_mask,
+                                         const Sr &sr, uint64_t i0, int o, SrC &cc)
+{
+    Chunk<T> xf[U][KMAX];
+    unsigned fmask = 0;
+    if constexpr (PROG == 0) {
+#pragma unroll
+        for (int q = 0; q < KMAX; ++q) {
+            if (q < k && fold[q]) {
+                fmask |= 1u << q;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const long c = c0 + (long)u * 256;
+                    if (c < nvec) xf[u][q] = ld_chunk<T, NT>(fold[q], c);
+                }
+            }
+        }
+    }
+    // a lone leaf is copied as it is (scalar_elem_sr)
+    if (PROG == 0 && k == 1 && !fmask) return;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        uint32_t rb[4];
+        sr_word_bits<T, 4>(sr, i0 + (uint64_t)(c0 + (long)u * 256) * CG<T>::v, o, cc, rb);
+        sr_chunk<T, KMAX, PROG>(x[u], xf[u], fmask, k, tree_mask, chain_mask, rb);
+    }
+}
+
 // The fixed full tree over the aligned body only: what a large C3 / C5
 // combine is once the plan's blocks are 16-byte aligned and whole (no head,
 // no tail, no folded leaves).  Its prologue is a handful of scalar loads
@@ -217,6 +253,9 @@ struct BodyParams {
 };
 struct SBodyParams : BodyParams {
     Scl sc;      // SParams::sc (no leaf of a body launch is folded: fscale is not read)
+};
+struct RBodyParams : BodyParams {
+    Sr sr;       // RParams::sr (a body launch has no head: chunk c begins at element sr.first + c * V)
 };
 
 // 56 KiB of static LDS per block: 2 resident blocks (8 waves) per CU.
@@ -240,14 +279,16 @@ __device__ __forceinline__ float ld_f32side(const char *p, long i)
 
 // ---------------------------------------------------------------------------
 // The kernels that take Params / BodyParams are defined in mvx_ops_kern_def.h,
-// which is read twice: once for every op there was (MVX_KP = Params), once
+// which is read three times: once for every op there was (MVX_KP = Params), once
 // more for the scaled sum, whose kernels take the same structs with its
-// scales behind (SParams, SBodyParams) as overloads of the same templates.
+// scales behind (SParams, SBodyParams) as overloads of the same templates, and
+// once for the stochastically rounded sum (RParams, RBodyParams: its seed and
+// first index).
 // A field added to Params itself moves the hidden arguments behind it into
 // another cache line of the kernarg segment, which every launch of every
 // kernel then fetches (0.3 us a launch on the 256 MiB MPI_SUM); and a body
 // function shared by two thin kernels compiles to other code than the kernel
-// did.  Read twice, the existing kernels stay what they were, byte for byte.
+// did.  Read again, the existing kernels stay what they were, byte for byte.
 #define MVX_KP Params
 #define MVX_KBP BodyParams
 #include "mvx_ops_kern_def.h"
@@ -255,6 +296,11 @@ __device__ __forceinline__ float ld_f32side(const char *p, long i)
 #undef MVX_KBP
 #define MVX_KP SParams
 #define MVX_KBP SBodyParams
+#include "mvx_ops_kern_def.h"
+#undef MVX_KP
+#undef MVX_KBP
+#define MVX_KP RParams
+#define MVX_KBP RBodyParams
 #include "mvx_ops_kern_def.h"
 #undef MVX_KP
 #undef MVX_KBP

@@ -1,5 +1,5 @@
-// mvx_ops_kern_def.h -- the kernels of mvx_ops_kern.h that take MVX_KP (Params
-// or SParams) or MVX_KBP (BodyParams or SBodyParams), and the element path
+// mvx_ops_kern_def.h -- the kernels of mvx_ops_kern.h that take MVX_KP (Params,
+// SParams or RParams) or MVX_KBP (BodyParams, SBodyParams or RBodyParams), and the element path
 // they share.  No include guard: mvx_ops_kern.h reads it once per pair of
 // types, inside namespace mvx (the reason is given there).
 
@@ -75,6 +75,28 @@ __device__ __forceinline__ void scalar_elem_scl(const MVX_KP &P, long i, unsigne
     narrow_elt(reinterpret_cast<T *>(P.dst) + i, y[0][0]);
 }
 
+// OSR's scalar_elem_acc: the same f32 value, narrowed with the bits of element
+// sr.first + i of the reduced vector
+template <int O, typename T, int KMAX>
+__device__ __forceinline__ void scalar_elem_sr(const MVX_KP &P, long i)
+{
+    const Sr &sr = sr_of<O>(P);
+    if (P.k == 1 && !P.fold[0]) {   // copied, bits and all
+        store_elt(reinterpret_cast<T *>(P.dst) + i, reinterpret_cast<const T *>(P.src[0])[i]);
+        return;
+    }
+    float y[KMAX][1];
+#pragma unroll
+    for (int q = 0; q < KMAX; ++q) {
+        if (q < P.k) {
+            y[q][0] = widen_elt(reinterpret_cast<const T *>(P.src[q]) + i);
+            if (P.fold[q]) y[q][0] = accf<OSR>(y[q][0], widen_elt(reinterpret_cast<const T *>(P.fold[q]) + i));
+        }
+    }
+    acc_steps<OSR, KMAX, 1, 0>(y, P.k, P.tree_mask, P.chain_mask);
+    narrow_elt_sr(reinterpret_cast<T *>(P.dst) + i, y[0][0], sr_elt_bits<T>(sr, sr.first + (uint64_t)i));
+}
+
 // PROG = 0: the program comes from the masks (any chain of trees over
 // k <= KMAX leaves); PROG = 1: the full balanced tree over exactly KMAX
 // leaves, steps fixed at compile time -- the Allreduce / Reduce order at
@@ -93,10 +115,12 @@ k_combine(const MVX_KP P)
     const long tid = (long)blockIdx.x * 256 + threadIdx.x;
     const long nthr = (long)gridDim.x * 256;
     unsigned am = 0;   // OSCL: the lane's amax over everything it stores
+    [[maybe_unused]] SrC cc = src_none();   // OSR: the lane's hash constant
 
     if (!P.vec_ok) {  // operands misaligned against each other: element loads
         for (long i = tid; i < P.n; i += nthr) {
             if constexpr (O == OSCL) scalar_elem_scl<O, T, KMAX>(P, i, am);
+            else if constexpr (O == OSR) scalar_elem_sr<O, T, KMAX>(P, i);
             else scalar_elem<O, T, KMAX>(P, i);
         }
         if constexpr (O == OSCL) {
@@ -110,6 +134,7 @@ k_combine(const MVX_KP P)
         for (long s = tid; s < nscal; s += nthr) {
             const long i = s < P.head ? s : tail0 + (s - P.head);
             if constexpr (O == OSCL) scalar_elem_scl<O, T, KMAX>(P, i, am);
+            else if constexpr (O == OSR) scalar_elem_sr<O, T, KMAX>(P, i);
             else scalar_elem<O, T, KMAX>(P, i);
         }
     }
@@ -138,6 +163,11 @@ k_combine(const MVX_KP P)
         }
         if constexpr (acc_op<O, T>::v) {
             if constexpr (O == OSCL) batch_scl<T, KMAX, U, NT, PROG>(x, fold, c0, P.nvec, k, tmask, cmask, scl_of<O>(P), am);
+            else if constexpr (O == OSR) {
+                const uint64_t i0 = sr_of<O>(P).first + (uint64_t)P.head;   // the body's first element
+                batch_sr<T, KMAX, U, NT, PROG>(x, fold, c0, P.nvec, k, tmask, cmask, sr_of<O>(P), i0,
+                                               (int)(i0 & (Wide<T>::L - 1)), cc);
+            }
             else batch_acc<O, T, KMAX, U, NT, PROG>(x, fold, c0, P.nvec, k, tmask, cmask, P.divisor);
         } else {
 #pragma unroll
@@ -217,6 +247,7 @@ k_tree_body(const MVX_KBP P)
     if (P.nvec < 0) lds_cap[threadIdx.x] = 0;
     const long nthr = (long)gridDim.x * 256;
     unsigned am = 0;
+    [[maybe_unused]] SrC cc = src_none();
     for (long c0 = (long)blockIdx.x * (256 * U) + threadIdx.x; c0 < P.nvec; c0 += nthr * U) {
         Chunk<T> x[U][KMAX];
 #pragma unroll
@@ -234,6 +265,11 @@ k_tree_body(const MVX_KBP P)
                     if constexpr (O == OSCL) {
                         const unsigned m = scl_chunk<T, KMAX, 1>(x[u], x[u], 0u, KMAX, 0u, 0u, scl_of<O>(P));
                         am = m > am ? m : am;
+                    } else if constexpr (O == OSR) {
+                        uint32_t rb[4];
+                        sr_word_bits<T, 4>(sr_of<O>(P), sr_of<O>(P).first + (uint64_t)c * CG<T>::v,
+                                           (int)(sr_of<O>(P).first & (Wide<T>::L - 1)), cc, rb);
+                        sr_chunk<T, KMAX, 1>(x[u], x[u], 0u, KMAX, 0u, 0u, rb);
                     } else {
                         acc_chunk<O, T, KMAX, 1>(x[u], x[u], 0u, KMAX, 0u, 0u, P.divisor);
                     }
@@ -268,6 +304,7 @@ k_chain_body(const MVX_KBP P)
     const int k = KMAX == 8 ? P.k : KMAX;
     const long nthr = (long)gridDim.x * 256;
     unsigned am = 0;
+    [[maybe_unused]] SrC cc = src_none();
     for (long c0 = (long)blockIdx.x * (256 * U) + threadIdx.x; c0 < P.nvec; c0 += nthr * U) {
         Chunk<T> x[U][KMAX];
 #pragma unroll
@@ -286,6 +323,11 @@ k_chain_body(const MVX_KBP P)
                     if constexpr (O == OSCL) {
                         const unsigned m = scl_chunk<T, KMAX, 0>(x[u], x[u], 0u, k, 0u, (1u << k) - 2u, scl_of<O>(P));
                         am = m > am ? m : am;
+                    } else if constexpr (O == OSR) {
+                        uint32_t rb[4];
+                        sr_word_bits<T, 4>(sr_of<O>(P), sr_of<O>(P).first + (uint64_t)c * CG<T>::v,
+                                           (int)(sr_of<O>(P).first & (Wide<T>::L - 1)), cc, rb);
+                        sr_chunk<T, KMAX, 0>(x[u], x[u], 0u, k, 0u, (1u << k) - 2u, rb);
                     } else {
                         acc_chunk<O, T, KMAX, 0>(x[u], x[u], 0u, k, 0u, (1u << k) - 2u, P.divisor);
                     }
@@ -309,7 +351,8 @@ k_chain_body(const MVX_KBP P)
 // intermediates being f32 temporaries.  DIR = 0: narrow leaves (folds
 // allowed), f32 result, not narrowed; DIR = 1: f32 leaves, the result narrowed
 // once (OAVG, the last launch of such a program: divided, then narrowed; OSCL:
-// DIR = 0 scales the leaves, DIR = 1 rescales the value and takes amax).  A lane takes one 32-bit word of each narrow operand against L floats
+// DIR = 0 scales the leaves, DIR = 1 rescales the value and takes amax; OSR:
+// DIR = 1 alone, narrowed with the elements' bits).  A lane takes one 32-bit word of each narrow operand against L floats
 // of each f32 one (a dwordx4 for the 8-bit types, a dwordx2 for the 16-bit
 // ones).  Params: head elements lead to nvec such words where the narrow
 // side is 4-byte and the f32 side 4 * L-byte aligned (vec_ok), else every
@@ -352,6 +395,9 @@ k_combine_f32(const MVX_KP P)
                 if (scl_of<O>(P).amax) am = scl_amax(am, y[0]);
             }
             if constexpr (DIR == 0) reinterpret_cast<float *>(P.dst)[i] = y[0][0];
+            else if constexpr (O == OSR)
+                narrow_elt_sr(reinterpret_cast<T *>(P.dst) + i, y[0][0],
+                              sr_elt_bits<T>(sr_of<O>(P), sr_of<O>(P).first + (uint64_t)i));
             else narrow_elt(reinterpret_cast<T *>(P.dst) + i, y[0][0]);
         }
         if (!P.vec_ok) {
@@ -362,6 +408,7 @@ k_combine_f32(const MVX_KP P)
         }
     }
     const long nb = P.head * (long)sizeof(T), fb = P.head * 4;   // the body's byte offset on either side
+    [[maybe_unused]] SrC cc = src_none();
     for (long c = tid; c < P.nvec; c += nthr) {
         float y[KMAX][L];
 #pragma unroll
@@ -403,6 +450,11 @@ k_combine_f32(const MVX_KP P)
 #pragma unroll
             for (int j = 0; j < L; ++j) v[j] = y[0][j];
             reinterpret_cast<fL *>(P.dst + fb)[c] = v;
+        } else if constexpr (O == OSR) {
+            const uint64_t i0 = sr_of<O>(P).first + (uint64_t)P.head;
+            uint32_t rb[1];
+            sr_word_bits<T, 1>(sr_of<O>(P), i0 + (uint64_t)c * L, (int)(i0 & (L - 1)), cc, rb);
+            reinterpret_cast<uint32_t *>(P.dst + nb)[c] = sr_narrow<T>(y[0], rb[0]);
         } else {
             reinterpret_cast<uint32_t *>(P.dst + nb)[c] = Wide<T>::narrow(y[0]);
         }

@@ -3,7 +3,7 @@
 // (Config), the descriptor of one kernel instantiation (KVar), the families
 // and sets built from them, the element kinds and the per-op table units'
 // lookup functions.  Included by mvx_ops.hip (dispatch and launch policy) and
-// by mvx_ops_{cmp,arith,logic,loc,half,fp8,acc32,avg,scaled}.hip, which instantiate the kernels of
+// by mvx_ops_{cmp,arith,logic,loc,half,fp8,acc32,avg,scaled,sr}.hip, which instantiate the kernels of
 // mvx_ops_kern.h through the macros below, one translation unit each so that
 // they compile in parallel.
 #include <stdio.h>
@@ -112,12 +112,14 @@ struct KSet {
     int esize;
     int chunk;             // bytes per chunk (16, or the element if wider)
     const char *name;
+    bool sr;               // MVX_SR_SUM: the kernels take RParams / RBodyParams
 };
 
 // the overload of a kernel template that op O launches: the scaled sum's takes
-// SParams / SBodyParams (mvx_ops_kern.h)
-template <int O> using KFn = void (*)(const std::conditional_t<O == OSCL, SParams, Params>);
-template <int O> using KBodyFn = void (*)(const std::conditional_t<O == OSCL, SBodyParams, BodyParams>);
+// SParams / SBodyParams, the stochastically rounded sum's RParams /
+// RBodyParams (mvx_ops_kern.h)
+template <int O> using KFn = void (*)(const std::conditional_t<O == OSCL, SParams, std::conditional_t<O == OSR, RParams, Params>>);
+template <int O> using KBodyFn = void (*)(const std::conditional_t<O == OSCL, SBodyParams, std::conditional_t<O == OSR, RBodyParams, BodyParams>>);
 
 template <int O, typename T, int KMAX, int U, int NT, int PROG>
 static KVar kvar_combine()
@@ -197,13 +199,19 @@ static KSet kset(const char *name)
         s.tree4 = kfam<O, T, 4, 1, 1, 1>(FAM_TREE);
     } else {
         s.tree8 = kfam<O, T, 8, 1, 2, 1>(FAM_TREE);
-        s.tree4 = kfam<O, T, 4, 1, 2, 1>(FAM_TREE);
+        if constexpr (O != OSR) s.tree4 = kfam<O, T, 4, 1, 2, 1>(FAM_TREE);
     }
     s.chain8 = kchain<O, T, 8>();
-    s.chain4 = kchain<O, T, 4>();
-    if constexpr (alu_heavy<T>::v) {
+    if constexpr (O == OSR) {
+        // MVX_SR_SUM has no KMAX = 4 kernels: programs over 3 or 4 leaves run
+        // the masked program over 8 (nothing about it is tuned yet, and every
+        // instantiation is a kernel more to load and register in every process)
+        s.tree4 = s.chain4 = s.prog4 = s.prog;
+    } else if constexpr (alu_heavy<T>::v) {
+        s.chain4 = kchain<O, T, 4>();
         s.prog4 = kfam<O, T, 4, 1, 1, 0>(FAM_PROG);
     } else {
+        s.chain4 = kchain<O, T, 4>();
         s.prog4 = kfam<O, T, 4, 2, 2, 0>(FAM_PROG);
     }
     if constexpr (sizeof(T) == 4) {
@@ -214,14 +222,16 @@ static KSet kset(const char *name)
     s.f32side[0] = s.f32side[1] = KVar{};
     // (the scaled sum on float has no other format to go through: its f32 sides are its own kernels)
     if constexpr (acc_op<O, T>::v && narrow_float<T>::v) {
-        // (MVX_AVG's launches before the last are MVX_SUM_ACC32's: it has the f32-leaves form alone)
-        if constexpr (O != OAVG)
+        // (MVX_AVG's launches before the last are MVX_SUM_ACC32's, and so are
+        // MVX_SR_SUM's: they have the f32-leaves form alone)
+        if constexpr (O != OAVG && O != OSR)
             s.f32side[0] = {(const void *)static_cast<KFn<O>>(&k_combine_f32<O, T, 0>), &ksym<K_COMBINE_F32, O, T, 0>, 1, false, 1, 0, 1, MVX_COMBINE_KMAX};
         s.f32side[1] = {(const void *)static_cast<KFn<O>>(&k_combine_f32<O, T, 1>), &ksym<K_COMBINE_F32, O, T, 1>, 1, false, 1, 0, 1, MVX_COMBINE_KMAX};
     }
     s.esize = (int)sizeof(T);
     s.chunk = CG<T>::bytes;
     s.name = name;
+    s.sr = O == OSR;
     return s;
 }
 
@@ -297,5 +307,6 @@ const KSet *lookup_fp8(int op, int ek);     // every op on the 8-bit floats   mv
 const KSet *lookup_acc32(int op, int ek);   // MVX_SUM_ACC32, MVX_PROD_ACC32  mvx_ops_acc32.hip
 const KSet *lookup_avg(int ek);             // MVX_AVG                        mvx_ops_avg.hip
 const KSet *lookup_scaled(int ek);          // MVX_SCALED_SUM                 mvx_ops_scaled.hip
+const KSet *lookup_sr(int ek);              // MVX_SR_SUM                     mvx_ops_sr.hip
 
 }  // namespace mvx

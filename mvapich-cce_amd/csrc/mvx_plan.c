@@ -35,7 +35,7 @@
 #include <string.h>
 #include "mvx_coll.h"
 #include "mvx_hip.h"
-#include "mvx_internal.h"   /* mvxi_scaled */
+#include "mvx_internal.h"   /* mvxi_scaled, mvxi_sr */
 
 /* coll_table, intra_fns_new.c:129-132, flattened: the reference reads
  * row[-1] (the previous row's last entry) when p = 1. */
@@ -172,6 +172,8 @@ static int op_symmetric(int op, int dtype)
     int old = dtype, cnt = 1;
     /* a scaled sum (a handle of the user-op table): f32 adds of scaled leaves, where it is defined */
     if (mvxi_scaled(op)) return mvx_op_supported(MVX_SCALED_SUM, dtype);
+    /* a stochastically rounded sum: f32 adds, one rounding of the value */
+    if (mvxi_sr(op)) return mvx_op_supported(MVX_SR_SUM, dtype);
     /* an undefined pair leaves every inout operand as it is (global_ops.c's
      * default branches): the result is the inout leaf's, so roles matter */
     if (!mvx_op_supported(op, dtype)) return 0;

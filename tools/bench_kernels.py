@@ -19,7 +19,8 @@ configs; half runs only the 16-bit floating types against MPI_SHORT, fp8 only
 the 8-bit ones against MPI_UNSIGNED_CHAR, acc32 only MVX_SUM_ACC32 /
 MVX_PROD_ACC32 against MPI_SUM / MPI_PROD on the four narrow floating types,
 avg only MVX_AVG's 8-leaf tree against its sum twin (f32, E4M3), scaled only
-the scaled sum's tree and apply, with and without amax, against its twin.
+the scaled sum's tree and apply, with and without amax, against its twin, sr
+only the stochastically rounded sum's tree and apply against MVX_SUM_ACC32.
 """
 import importlib
 import json
@@ -172,8 +173,23 @@ def scaled(mvx):
                     warm=2, amax=word)
 
 
+def sr(mvx):
+    """The stochastically rounded sum next to MVX_SUM_ACC32, whose f32 value it
+    narrows: the 8 x 64 MiB tree and the 256 MiB apply on E4M3 and BF16 (seed 0,
+    first index 0: what the op runs with through op_combine / op_apply); each
+    pair three times over, twin first."""
+    for rep in range(3):
+        for t, tn in ((72, "f8e4m3"), (65, "bf16")):
+            for k, shape, kn, leaf in ((8, 0, "tree8", 64 * MIB), (2, 1, "apply", 256 * MIB)):
+                run(mvx, "R-%s-sum_acc32_%s-%d" % (kn, tn, rep), mvx.MVX_SUM_ACC32, t, k, shape, leaf, 2, reps=10, warm=2)
+                run(mvx, "R-%s-sr_%s-%d" % (kn, tn, rep), mvx.MVX_SR_SUM, t, k, shape, leaf, 2, reps=10, warm=2)
+
+
 def main():
     mvx = importlib.import_module("mvapich-cce_amd")
+    if "sr" in sys.argv[1:]:
+        sr(mvx)
+        return
     if "scaled" in sys.argv[1:]:
         scaled(mvx)
         return
